@@ -2,6 +2,16 @@
 pointmaze-large (pointmaze-large-navigate-v0), 1/2/4/8 MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload pointmaze|powder|gcsample]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set up, W warm-up
+steps, the K timed steps, the result line (``roofline.kernel_ms`` is then the
+HIP event span around the timed region / K, which costs no launch of its own).
+``--dump-outputs DIR`` writes what the last timed step returned to its caller
+as DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed seeded row sample
+of anything larger); the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.  Everything else this file
+measures (the "Extra fields" below) runs only with ``--full``.
 
 A step = one ``env.step(action)`` of all envs of this rank: one launch of
 ``maze_step_kernel`` through the C-ABI (Python -> ctypes -> libogbx), with the
@@ -23,7 +33,7 @@ A WORLD_SIZE that differs from --gpus, or more nccl (RCCL) ranks than visible
 GPUs, is refused (exit 2).  ``ranks_seen`` counts the ranks an untimed
 all-gather reached.
 
-Extra fields (not ``value``): the same workload replayed from a hipGraph and
+Extra fields (not ``value``; ``--full`` only): the same workload replayed from a hipGraph and
 as K fused steps per launch; ``roofline`` of maze_step_kernel (algorithmic
 87 B per env-step) from the smaller of two HIP event spans on the
 launch stream (the timed region / its steps, >= 1000 back-to-back launches /
@@ -154,10 +164,11 @@ def _ranks_seen(world, dev):
     return len({int(t.item()) for t in got})
 
 
-def _timed(fn, steps, world, dev, span=None):
+def _timed(fn, steps, world, dev, span=None, keep=None):
     """Wall time of `steps` calls between barrier + synchronize on both sides,
     max over ranks.  span (a list): receives the device time of the same
-    region from a HIP event pair on the launch stream, in ms.
+    region from a HIP event pair on the launch stream, in ms.  keep (a list):
+    receives what the last call returned (for --dump-outputs).
 
     Each rank's clock runs from the end of the leading barrier + synchronize
     to the end of its own trailing synchronize; the trailing barrier follows
@@ -169,9 +180,10 @@ def _timed(fn, steps, world, dev, span=None):
     if span is not None:
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record(torch.cuda.current_stream(dev))
+    last = None
     t0 = time.perf_counter()
     for i in range(steps):
-        fn(i)
+        last = fn(i)
     if span is not None:
         b.record(torch.cuda.current_stream(dev))
     torch.cuda.synchronize(dev)
@@ -179,6 +191,8 @@ def _timed(fn, steps, world, dev, span=None):
     _barrier(world)
     if span is not None:
         span.append(a.elapsed_time(b))
+    if keep is not None:
+        keep.append(last)
     return _max_over_ranks(dt, world, dev)
 
 
@@ -259,6 +273,79 @@ def _launch_ms(span_ms, steps, fn, launches, dev):
         kernel_ms_timed_region=timed, kernel_ms_back_to_back=b2b, kernel_ms_event_pair_median=med)
 
 
+def _kernel_time(args, span_ms, steps, fn, launches, dev):
+    """kernel_ms for the roofline.  A plain run prices the launch from the
+    timed region's own event span (no launch beyond the timed steps); --full
+    adds _launch_ms's back-to-back and event-pair passes."""
+    if args.full:
+        return _launch_ms(span_ms, steps, fn, launches, dev)
+    timed = span_ms / steps
+    return timed, dict(
+        kernel_ms_method=f'HIP event span around the {steps}-step timed region / steps; launch stream; includes the '
+                         'inter-launch dispatch gap (--full adds the back-to-back span)',
+        kernel_ms_timed_region=timed)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+_STEP_NAMES = ('obs', 'reward', 'terminated', 'truncated', 'info')
+
+
+def _named_outputs(ret):
+    """(name, tensor) pairs of what one timed call returned: a Gymnasium step
+    tuple (info's tensors as info_<key>) or a sampler's batch dict."""
+    if isinstance(ret, dict):
+        items = list(ret.items())
+    elif isinstance(ret, (tuple, list)):
+        names = _STEP_NAMES if len(ret) == len(_STEP_NAMES) else [f'out{i}' for i in range(len(ret))]
+        items = list(zip(names, ret))
+    else:
+        items = [('out', ret)]
+    flat = []
+    for k, v in items:
+        if isinstance(v, dict):
+            flat += [(f'{k}_{kk}', vv) for kk, vv in v.items() if torch.is_tensor(vv)]
+        elif torch.is_tensor(v):
+            flat.append((str(k), v))
+    return [(k.replace('/', '_'), v) for k, v in flat]
+
+
+def _dump_outputs(path, ret, rank=0, world=1, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write the tensors of `ret` (what the last timed call
+    handed its caller) as path/<name>.npy (<name>.rank<r>.npy under several
+    ranks).  64-bit values are stored as float64, everything else as float32.
+    When the stored arrays would exceed `limit` bytes, every array keeps the
+    same fraction of its rows (axis 0), drawn once from RandomState(0): a
+    fixed sample, the same rows for arrays of the same length.  Returns
+    {name: stored shape}."""
+    flat = _named_outputs(ret)
+    os.makedirs(path, exist_ok=True)
+    wide = (torch.float64, torch.int64)
+    total = sum(v.numel() * (8 if v.dtype in wide else 4) for _, v in flat)
+    limit -= 256 * len(flat)  # the .npy headers count too
+    shapes = {}
+    for name, v in flat:
+        v = v.detach()
+        if total > limit and v.dim() >= 1 and v.shape[0] > 1:
+            rows = max(1, int(v.shape[0] * limit / total))
+            idx = np.sort(np.random.RandomState(0).choice(v.shape[0], rows, replace=False))
+            v = v[torch.as_tensor(idx, device=v.device)]
+        a = v.to('cpu').to(torch.float64 if v.dtype in wide else torch.float32).numpy()
+        np.save(os.path.join(path, f'{name}.npy' if world == 1 else f'{name}.rank{rank}.npy'), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
+def _timed_steps(args, step, steps, world, rank, dev):
+    """The timed region of every workload: (wall seconds, device span in ms);
+    then, with --dump-outputs, the last step's outputs go to disk before
+    anything else runs on the handle."""
+    span, keep = [], []
+    dt = _timed(step, steps, world, dev, span, keep)
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, keep[0], rank, world)
+    return dt, span[0]
+
+
 def _traffic(kernel, workload, units, world):
     """HBM bytes per launch of `kernel` from the committed rocprofv3 PMC summary
     (profiles/traffic.json, written by scripts/prof_summary.py from separate
@@ -287,21 +374,20 @@ def bench_pointmaze(args, world, rank, dev):
     views = list(actions.unbind(0))  # the ring's [n, 2] rows, indexed without a tensor op
 
     def step(i):
-        env.step(views[i % ring])
+        return env.step(views[i % ring])
 
     for i in range(args.warmup):
         step(i)
-    span = []
-    dt = _timed(step, args.steps, world, dev, span)
+    dt, span_ms = _timed_steps(args, step, args.steps, world, rank, dev)
     value = total * args.steps / dt
     ms_per_step = dt / args.steps * 1e3
 
     # kernel duration for the roofline (the timed region's device span)
-    kern_ms, kern_info = _launch_ms(span[0], args.steps, step, max(1000, min(args.steps, 2000)), dev)
+    kern_ms, kern_info = _kernel_time(args, span_ms, args.steps, step, max(1000, min(args.steps, 2000)), dev)
     alg_bytes = 87 * n  # 87 B per env-step
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
 
-    extra = {'host_us_per_step': _host_us_per_call(step, 200, dev)}
+    extra = {'host_us_per_step': _host_us_per_call(step, 200, dev)} if args.full else {}
     if args.no_extras:
         return _finish_pointmaze(args, world, rank, total, n, value, ms_per_step, kern_ms, alg_bytes, achieved,
                                  extra, env, kern_info)
@@ -525,13 +611,12 @@ def bench_pointmaze_n1(args, world, rank, dev):
     actions = (torch.rand(ring, 1, 2, generator=gen) * 2 - 1).float().to(dev)
 
     def step(i):
-        env.step(actions[i % ring])
+        return env.step(actions[i % ring])
 
     for i in range(args.warmup):
         step(i)
-    span = []
-    dt = _timed(step, args.steps, world, dev, span)
-    kern_ms, kern_info = _launch_ms(span[0], args.steps, step, 1000, dev)
+    dt, span_ms = _timed_steps(args, step, args.steps, world, rank, dev)
+    kern_ms, kern_info = _kernel_time(args, span_ms, args.steps, step, 1000, dev)
     result = dict(
         metric='env steps/sec, pointmaze-medium-navigate-v0, N=1 env (Gymnasium surface)',
         value=args.steps * world / dt, unit='env_steps/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
@@ -600,17 +685,16 @@ def bench_gcsample(args, world, rank, dev):
 
     def step(i):
         # refill the previous batch in place (stream ordered; no per-call allocation)
-        gc.sample(B, out=batch)
+        return gc.sample(B, out=batch)
 
     def step_fresh(i):
         gc.sample(B)
 
     for i in range(args.warmup):
         step(i)
-    span = []
-    dt = _timed(step, args.steps, world, dev, span)
+    dt, span_ms = _timed_steps(args, step, args.steps, world, rank, dev)
     value = B * args.steps * world / dt
-    kern_ms, kern_info = _launch_ms(span[0], args.steps, step, 1000, dev)
+    kern_ms, kern_info = _kernel_time(args, span_ms, args.steps, step, 1000, dev)
     per_sample = 2424  # algorithmic bytes per sample (humanoid layout)
     achieved = per_sample * B / (kern_ms * 1e-3) / 1e9
     NB = 256
@@ -618,7 +702,7 @@ def bench_gcsample(args, world, rank, dev):
     def fused(i):
         gc.sample(B, num_batches=NB)
 
-    extra = {'host_us_per_call': _host_us_per_call(step, 200, dev)}
+    extra = {'host_us_per_call': _host_us_per_call(step, 200, dev)} if args.full else {}
     if not args.no_extras:
         fdt0 = _timed(step_fresh, args.steps, world, dev)
         extra['fresh_alloc_samples_per_s'] = B * args.steps * world / fdt0
@@ -675,18 +759,17 @@ def bench_hgcsample(args, world, rank, dev):
     batch = hgc.sample(B)
 
     def step(i):
-        hgc.sample(B, out=batch)
+        return hgc.sample(B, out=batch)
 
     for i in range(args.warmup):
         step(i)
-    span = []
-    dt = _timed(step, args.steps, world, dev, span)
-    kern_ms, kern_info = _launch_ms(span[0], args.steps, step, 1000, dev)
+    dt, span_ms = _timed_steps(args, step, args.steps, world, rank, dev)
+    kern_ms, kern_info = _kernel_time(args, span_ms, args.steps, step, 1000, dev)
     # 12 gathered 276-B observation rows + actions 84 + terminals/valids 8,
     # read and written, + valid_idxs/traj_end lookups 16 + 9 x 8-B scalars written
     per_sample = 2 * (12 * 276 + 84 + 8) + 16 + 72
     achieved = per_sample * B / (kern_ms * 1e-3) / 1e9
-    extra = {'host_us_per_call': _host_us_per_call(step, 200, dev)}
+    extra = {'host_us_per_call': _host_us_per_call(step, 200, dev)} if args.full else {}
     if not args.no_extras:
         NB = 128
         big = hgc.sample(B, num_batches=NB)
@@ -800,19 +883,18 @@ def bench_powder(args, world, rank, dev, level='easy'):
     actions = (torch.rand(ring, n, device=dev, generator=gen) * hi).to(torch.int32)
 
     def step(i):
-        env.step(actions[i % ring])
+        return env.step(actions[i % ring])
 
     for i in range(args.warmup):
         step(i)
     steps = args.steps - args.steps % 3 if args.steps >= 3 else args.steps
-    span = []
-    dt = _timed(step, steps, world, dev, span)
+    dt, span_ms = _timed_steps(args, step, steps, world, rank, dev)
     value = n * steps * world / dt
     # device time per step of the timed region itself (one HIP event pair on
     # the launch stream around it): the world's contents, and with them the
     # forward's cost, drift over an episode, so a separate window would price
     # different states; the mean also spans whole 3-step action cycles
-    kern_ms = span[0] / steps
+    kern_ms = span_ms / steps
     # algorithmic bytes per env-step.  easy: obs write H*W*6, world read H*W,
     # world write H*W on one step in three, action 4, reward 4, flags 3, ctrl
     # 16.  medium/hard (render-cache design), per cell and 3-step
@@ -1003,14 +1085,13 @@ def bench_antmaze(args, world, rank, dev):
     rq, rv = list(ring_q.unbind(0)), list(ring_v.unbind(0))
 
     def step(i):
-        env.wrap_step(rq[i % R], rv[i % R])
+        return env.wrap_step(rq[i % R], rv[i % R])
 
     for i in range(args.warmup):
         step(i)
-    span = []
-    dt = _timed(step, args.steps, world, dev, span)
+    dt, span_ms = _timed_steps(args, step, args.steps, world, rank, dev)
     value = n * world * args.steps / dt
-    kern_ms, kern_info = _launch_ms(span[0], args.steps, step, max(1000, min(args.steps, 2000)), dev)
+    kern_ms, kern_info = _kernel_time(args, span_ms, args.steps, step, max(1000, min(args.steps, 2000)), dev)
     per = 3 * ANT_BYTES + 16 + 8 + 7
     achieved = per * n / (kern_ms * 1e-3) / 1e9
     extra = {}
@@ -1067,7 +1148,8 @@ def cpu_baseline_antmaze(n, args):
                 sample=f'{steps} steps x {n} envs of the wrapper with auto-reset ({dt:.1f} s)')
 
 
-def main():
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=2000)
@@ -1077,15 +1159,23 @@ def main():
                              'hgcsample', 'antmaze'])
     ap.add_argument('--num-envs', type=int, default=65536)
     ap.add_argument('--ring', type=int, default=128)
-    ap.add_argument('--cpu-seconds', type=float, default=12.0)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='only the timed single-step workload (profiling runs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (at most 64 MB)")
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline figure: CPU baseline, fused / graph variants, the '
+                         'eval reduction, back-to-back kernel timing, host cost per call')
+    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='with --full: length of the CPU baseline loop')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
+    ap.add_argument('--no-extras', action='store_true',
+                    help='with --full: leave the fused / eval extras out (profiling runs)')
     ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'],
                     help="'gloo' rehearses the multi-rank path with ranks sharing GPUs")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: the timed steps and nothing beside them
+        args.no_extras = args.no_cpu_baseline = True
     # before any HIP call: refuse a mismatched layout, or start the N ranks
     if _check_world(args.gpus, args.dist_backend) == 'self-launch':
-        rc, _ = _self_launch(args.gpus, sys.argv[1:])
+        rc, _ = _self_launch(args.gpus, argv)
         sys.exit(rc)
     world, rank, local = _dist_init(args.dist_backend)
     dev = torch.device('cuda', local)

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 for wl in pointmaze powder gcsample; do
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29533 bench.py --gpus 2 --steps 120 --warmup 10 --dist-backend gloo --workload $wl \
+    --master-port 29533 bench.py --full --gpus 2 --steps 120 --warmup 10 --dist-backend gloo --workload $wl \
     --num-envs 16384 > gpurun_out/dist_$wl.log 2>&1 || { tail -30 gpurun_out/dist_$wl.log; exit 1; }
   grep '^{' gpurun_out/dist_$wl.log | cut -c1-400
 done

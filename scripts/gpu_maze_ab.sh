@@ -10,7 +10,7 @@ LIBS=${LIBS:-"ogbench_amd/libogbx.so $(ls _abx/libogbx_*.so 2>/dev/null | tr '\n
 for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in $LIBS; do
     for N in ${NS:-65536 8192}; do
-      OGBX_LIB=$PWD/$lib timeout -k 10 120 python bench.py --num-envs $N --no-extras --no-cpu-baseline \
+      OGBX_LIB=$PWD/$lib timeout -k 10 120 python bench.py --full --num-envs $N --no-extras --no-cpu-baseline \
         > gpurun_out/ab.log 2>&1 || { tail -20 gpurun_out/ab.log; exit 4; }
       python - gpurun_out/ab.log "$lib" <<'PY'
 import json, sys

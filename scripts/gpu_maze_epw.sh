@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 for N in ${NS:-8192 16384 32768}; do
   for E in ${EPWS:-64 32 16}; do
-    OGBX_EPW=$E timeout -k 10 120 python bench.py --num-envs $N --steps 2000 --no-extras --no-cpu-baseline \
+    OGBX_EPW=$E timeout -k 10 120 python bench.py --full --num-envs $N --steps 2000 --no-extras --no-cpu-baseline \
       > gpurun_out/epw.log 2>&1 || { tail -20 gpurun_out/epw.log; exit 4; }
     python - gpurun_out/epw.log "$E" <<'PY'
 import json, sys

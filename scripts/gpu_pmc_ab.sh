@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/pmcab
 export TMPDIR=/tmp
-ARGS="--workload pointmaze --steps 200 --warmup 100 --no-cpu-baseline --no-extras ${BENCH_ARGS:-}"
+ARGS="--full --workload pointmaze --steps 200 --warmup 100 --no-cpu-baseline --no-extras ${BENCH_ARGS:-}"
 if [ "${LIST:-0}" = 1 ]; then timeout -s KILL 60 rocprofv3 -L > gpurun_out/pmcab/counters.txt 2>&1; fi
 P1="SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_WAIT_INST_ANY"
 P2=${P2:-"SQ_WAVES GRBM_GUI_ACTIVE GRBM_COUNT SQ_BUSY_CYCLES SQ_CYCLES"}

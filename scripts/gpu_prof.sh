@@ -14,7 +14,7 @@ ROUND=${ROUND:-r01}
 STEPS=${STEPS:-300}
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-ARGS="--workload $WL --steps $STEPS --warmup ${WARMUP:-100} --no-cpu-baseline --no-extras ${BENCH_ARGS:-}"
+ARGS="--full --workload $WL --steps $STEPS --warmup ${WARMUP:-100} --no-cpu-baseline --no-extras ${BENCH_ARGS:-}"
 TAG=${TAG:-$WL}
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run --output-format csv -- \
   python3 bench.py $ARGS > gpurun_out/prof_${TAG}.log 2>&1 || exit $?

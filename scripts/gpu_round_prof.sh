@@ -3,7 +3,8 @@
 # bench workload in $WLS (default: all), then the default bench line.
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}  # logs of this script
+mkdir -p "$OUT"
 WLS=${WLS:-"pointmaze powder powder-medium powder-hard gcsample hgcsample antmaze"}
 for wl in $WLS; do
   case $wl in
@@ -18,6 +19,6 @@ for wl in $WLS; do
   WL=$wl KERNEL=$K STEPS=$S bash scripts/gpu_prof.sh || exit $?
 done
 if [ "${DEFAULT_BENCH:-1}" = 1 ]; then
-  timeout -k 10 400 python bench.py > gpurun_out/bench_default.log 2>&1 || { tail -20 gpurun_out/bench_default.log; exit 1; }
-  grep '^{' gpurun_out/bench_default.log
+  timeout -k 10 400 python bench.py --full > $OUT/bench_default.log 2>&1 || { tail -20 $OUT/bench_default.log; exit 1; }
+  grep '^{' $OUT/bench_default.log
 fi

@@ -286,6 +286,19 @@ def main_full():
     print('powder full golden:', len(out), 'arrays')
 
 
+def main_blur():
+    """The velocity blur: sim.conv2d (3x3 ones / 18, padding 1) on a sparse
+    random field, input and output (tests/golden/powder_blur_golden.npz); pins
+    the summation order of oracle/powder_full_np.blur."""
+    sim, _ = reference_modules()
+    rng = np.random.RandomState(3)
+    x = (rng.normal(0, 3, (2, 1, 32, 32)) * (rng.rand(2, 1, 32, 32) < 0.6)).astype(np.float32)
+    ref = sim.conv2d(x, np.ones((1, 1, 3, 3), np.float32) / 18, padding=1)[:, 0]
+    np.savez_compressed(os.path.join(OUT, 'powder_blur_golden.npz'), x=x, ref=ref)
+    print('powder blur golden:', x.shape, ref.shape, ref.dtype)
+
+
 if __name__ == '__main__':
     main()
     main_full()
+    main_blur()

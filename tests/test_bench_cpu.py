@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -76,3 +77,51 @@ def test_strong_scaling_shards_cover_the_total():
         for (b0, n0), (b1, _) in zip(spans, spans[1:]):
             assert b0 + n0 == b1
         assert all(n % 64 == 0 for _, n in spans)  # whole waves per rank
+
+
+def test_dump_outputs_names_dtypes_and_fixed_sample(tmp_path):
+    # a step tuple: info's tensors are flattened, 64-bit values stay 64-bit,
+    # everything else is stored as float32
+    g = torch.Generator().manual_seed(0)
+    obs = torch.rand(1000, 4, dtype=torch.float64, generator=g)
+    ret = (obs, torch.rand(1000, generator=g), torch.arange(1000) % 3 == 0, torch.zeros(1000, dtype=torch.bool),
+           {'success': torch.arange(1000) % 2 == 0, 'note': 'not a tensor'})
+    shapes = bench._dump_outputs(str(tmp_path / 'all'), ret)
+    assert shapes == {'obs': [1000, 4], 'reward': [1000], 'terminated': [1000], 'truncated': [1000],
+                      'info_success': [1000]}
+    got = {k: np.load(tmp_path / 'all' / f'{k}.npy') for k in shapes}
+    assert got['obs'].dtype == np.float64 and np.array_equal(got['obs'], obs.numpy())
+    assert got['reward'].dtype == np.float32 and np.array_equal(got['reward'], ret[1].numpy())
+    assert got['terminated'].dtype == np.float32 and np.array_equal(got['terminated'], ret[2].numpy())
+    # over the size limit: the same seeded rows of every array, the same on every call, within the limit
+    limit = 8000
+    s1 = bench._dump_outputs(str(tmp_path / 's1'), ret, limit=limit)
+    s2 = bench._dump_outputs(str(tmp_path / 's2'), ret, limit=limit)
+    assert s1 == s2 and 1 < s1['obs'][0] < 1000 and s1['obs'][0] == s1['reward'][0]
+    sub = {k: np.load(tmp_path / 's1' / f'{k}.npy') for k in s1}
+    assert sum(v.nbytes for v in sub.values()) <= limit
+    for k in sub:
+        assert np.array_equal(sub[k], np.load(tmp_path / 's2' / f'{k}.npy'))
+    rows = np.flatnonzero((obs.numpy()[:, None, :] == sub['obs'][None]).all(-1).any(1))
+    assert len(rows) == s1['obs'][0] and np.array_equal(sub['reward'], ret[1].numpy()[rows])
+    # a sampler's batch dict, several ranks: one file per name and rank
+    bench._dump_outputs(str(tmp_path / 'r'), {'actor/goals': torch.ones(3, 2), 'idxs': torch.arange(3)}, rank=1, world=2)
+    assert sorted(os.listdir(tmp_path / 'r')) == ['actor_goals.rank1.npy', 'idxs.rank1.npy']
+    assert np.load(tmp_path / 'r' / 'idxs.rank1.npy').dtype == np.float64
+
+
+def test_plain_run_switches_everything_else_off(monkeypatch):
+    # without --full the parsed options ask for no extras and no CPU baseline
+    seen = {}
+
+    def fake(args, world, rank, dev):
+        seen.update(vars(args))
+        raise SystemExit(0)
+
+    monkeypatch.setattr(bench, 'bench_pointmaze', fake)
+    monkeypatch.setattr(bench, '_dist_init', lambda backend: (1, 0, 0))
+    for argv, full in ((['--steps', '7'], False), (['--steps', '7', '--full'], True)):
+        with pytest.raises(SystemExit):
+            bench.main(argv + ['--dist-backend', 'gloo'])  # (the nccl layout check wants a visible GPU)
+        assert seen['steps'] == 7 and seen['full'] is full
+        assert seen['no_extras'] is (not full) and seen['no_cpu_baseline'] is (not full)

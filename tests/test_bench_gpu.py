@@ -1,13 +1,15 @@
 """GPU: bench.py keeps the driver's output contract (one JSON line with the
-metric, value, roofline and cpu_baseline fields) and its per-launch time never
-exceeds the timed region's per-step time.  Short runs of the default workload
-and of the antmaze wrapper workload, each in a child process."""
+metric, value, roofline and, under --full, cpu_baseline fields) and its
+per-launch time never exceeds the timed region's per-step time.  Short runs of
+the default workload and of the antmaze wrapper workload, each in a child
+process; a plain run's leanness and its --dump-outputs files in this process."""
 
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +40,7 @@ def _contract(r):
 
 
 def test_default_bench_line():
-    r = _run('--steps', '1000', '--warmup', '50', '--cpu-seconds', '2')
+    r = _run('--steps', '1000', '--warmup', '50', '--cpu-seconds', '2', '--full')
     _contract(r)
     assert r['metric'].startswith('env steps/sec at N=65536 parallel envs, pointmaze-large')
     assert r['config']['total_envs'] == 65536 and r['scaling'] == 'strong' and r['dtype'] == 'f64'
@@ -52,7 +54,7 @@ def test_two_rank_line_without_a_launcher():
     # (gloo, both on this box's GPU) and rank 0's line covers the 2-rank job
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dist-backend', 'gloo',
-                          '--steps', '20', '--warmup', '5'], cwd=ROOT, env=env, capture_output=True, text=True,
+                          '--steps', '20', '--warmup', '5', '--full'], cwd=ROOT, env=env, capture_output=True, text=True,
                          timeout=400)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
@@ -69,3 +71,39 @@ def test_antmaze_bench_line():
     r = _run('--workload', 'antmaze', '--steps', '1000', '--warmup', '50', '--no-cpu-baseline')
     _contract(r)
     assert r['config']['num_envs_per_gpu'] == 16384 and r['roofline']['kernel'] == 'ant_step_kernel'
+
+
+def test_plain_run_is_lean_and_dumps_reproducible_outputs(gpu, tmp_path, capsys):
+    # a plain run: the timed steps only (no CPU baseline, no extras, no launch
+    # beyond warm-up + steps for the roofline), --steps is the timed step count,
+    # and --dump-outputs writes what the last timed env.step returned; a second
+    # run with the same arguments starts from the same inputs, so every array
+    # is equal bit for bit
+    sys.path.insert(0, ROOT)
+    import bench
+
+    n, steps = 8192 + 64, 37  # two shards of the action ring's 8192-env generation blocks
+    lines, dumps = [], []
+    for d in ('a', 'b'):
+        bench.main(['--gpus', '1', '--steps', str(steps), '--warmup', '5', '--num-envs', str(n),
+                    '--dump-outputs', str(tmp_path / d)])
+        out = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith('{')]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+        dumps.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    r = lines[0]
+    _contract(r)
+    assert r['steps'] == steps and r['warmup'] == 5 and r['unit'] == 'env_steps/s' and r['dtype'] == 'f64'
+    assert abs(r['value'] - n * 1e3 / r['ms_per_step']) <= 1e-9 * r['value']
+    assert 'cpu_baseline' not in r and r['extra'] == {}
+    assert 'kernel_ms_back_to_back' not in r['roofline']
+    assert r['roofline']['kernel_ms'] == r['roofline']['kernel_ms_timed_region']
+    a, b = dumps
+    assert set(a) == {'obs.npy', 'reward.npy', 'terminated.npy', 'truncated.npy', 'info_success.npy',
+                      'info_final_observation.npy'} == set(b)
+    assert a['obs.npy'].shape == (n, 2) and a['obs.npy'].dtype == np.float64
+    assert a['terminated.npy'].shape == (n,) and a['terminated.npy'].dtype == np.float32
+    assert np.isfinite(a['obs.npy']).all() and np.ptp(a['obs.npy'][:, 0]) > 1.0  # envs really moved apart
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_LIMIT_BYTES
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
