@@ -957,6 +957,159 @@ static bool periodic_ok(const ogbx_gc_buffer& b) {
          npick == (b.num_rows / b.period) * b.period_picks;
 }
 
+// ------------------------------------------------------------ argument checks
+// Every check of the GC / HGC entry points lives here, once; an entry point
+// runs its checks before its first HIP call.  `who` is the entry point's name.
+#define GC_TRY(expr)                       \
+  do {                                     \
+    if (ogbx_status _st = (expr)) return _st; \
+  } while (0)
+
+static std::string named(const char* who, const char* what) { return std::string(who) + ": " + what; }
+
+static ogbx_status check_buffer(const ogbx_gc_buffer* buf) {
+  OGBX_CHECK(buf->num_rows > 0 && buf->traj_end, OGBX_EINVAL, "empty trajectory buffer");
+  OGBX_CHECK(buf->valid_idxs == nullptr || buf->num_valid > 0, OGBX_EINVAL,
+             "no valid transitions in the dataset");
+  OGBX_CHECK(periodic_ok(*buf), OGBX_EINVAL, "ogbx_gc_buffer: inconsistent period fields");
+  return OGBX_OK;
+}
+
+// The batch shape and the column descriptors (select in [0, max_select]),
+// copied into the kernel-argument table *cc.
+static ogbx_status check_columns(const ogbx_gc_column* cols, int32_t num_cols, int64_t batch, int64_t num_batches,
+                                 int max_select, const char* who, GcColumns* cc) {
+  OGBX_CHECK(num_cols >= 0 && num_cols <= kGcMaxCols, OGBX_EINVAL, named(who, "at most 32 columns"));
+  OGBX_CHECK(batch > 0 && num_batches > 0, OGBX_EINVAL, "batch and num_batches must be > 0");
+  for (int i = 0; i < num_cols; ++i) {
+    const ogbx_gc_column& c = cols[i];
+    OGBX_CHECK(c.src_stride == 0 || c.src_stride >= c.row_bytes, OGBX_EINVAL,
+               named(who, "src_stride below row_bytes"));
+    OGBX_CHECK(c.src && c.dst && c.row_bytes > 0 && c.select >= 0 && c.select <= max_select, OGBX_EINVAL,
+               named(who, "bad column descriptor"));
+    cc->c[i] = c;
+  }
+  return OGBX_OK;
+}
+
+// The look-ahead kernels run one sample per workgroup and read one selector
+// buffer while they write the other.
+static ogbx_status check_ahead(int64_t total, const int64_t* ahead_in, const int64_t* ahead_out, const char* who) {
+  OGBX_CHECK(total <= kGcAheadMaxSamples, OGBX_EINVAL,
+             named(who, "at most 1024 samples per call (one per workgroup)"));
+  OGBX_CHECK(ahead_in != ahead_out || ahead_in == nullptr, OGBX_EINVAL,
+             named(who, "ahead_in and ahead_out must differ"));
+  return OGBX_OK;
+}
+
+static ogbx_status check_hgc_config(const ogbx_hgc_config* hcfg, const char* who) {
+  OGBX_CHECK(hcfg->hv_mask_table && hcfg->hv_reward_table && hcfg->lv_mask_table && hcfg->lv_reward_table,
+             OGBX_EINVAL, named(who, "missing reward/mask tables"));
+  OGBX_CHECK(hcfg->value_subgoal_steps >= 0 && hcfg->low_subgoal_steps >= 0 && hcfg->actor_subgoal_steps >= 0,
+             OGBX_EINVAL, named(who, "negative subgoal steps"));
+  OGBX_CHECK(!hcfg->has_low_value_goals || (hcfg->low_discount > 0.0 && hcfg->low_discount < 1.0), OGBX_EINVAL,
+             named(who, "low_discount must be in (0, 1)"));
+  return OGBX_OK;
+}
+
+static ogbx_status check_hgc_outputs(const ogbx_hgc_outputs* out, const char* who) {
+  OGBX_CHECK(out && out->high_value_offsets && out->high_value_subgoal_steps && out->high_value_masks &&
+                 out->high_value_rewards && out->low_value_subgoal_steps && out->low_value_masks &&
+                 out->low_value_rewards && out->masks && out->rewards,
+             OGBX_EINVAL, named(who, "missing scalar output"));
+  return OGBX_OK;
+}
+
+// ------------------------------------------------- derived launch parameters
+// tile: one sample per workgroup up to 1024 samples (B = 1024: 1,024
+// workgroups of 256 threads; measured against 2 and 4 samples per workgroup
+// and 64- to 1024-thread workgroups), then up to 64 per workgroup
+static int64_t gc_tile(int64_t total) { return std::clamp<int64_t>(total / 1024, 1, kGcMaxTile); }
+
+// What a (seed, config) fixes for every call: the Philox key and the
+// log(1 - p) terms of the geometric draws (p = 1 - discount).
+struct GcParams {
+  uint32_t k0 = 0, k1 = 0;
+  double v_log_q = 0, a_log_q = 0, l_log_q = 0;
+};
+
+static GcParams gc_params(uint64_t seed, const ogbx_gc_config& cfg, const ogbx_hgc_config* hcfg) {
+  GcParams pr;
+  seed_key(seed, hcfg ? kTagHgcSample : kTagGcSample, &pr.k0, &pr.k1);
+  pr.v_log_q = std::log(1.0 - (1.0 - cfg.value_discount));
+  pr.a_log_q = std::log(1.0 - (1.0 - cfg.actor_discount));
+  pr.l_log_q = (hcfg && hcfg->has_low_value_goals) ? std::log(1.0 - (1.0 - hcfg->low_discount)) : 0.0;
+  return pr;
+}
+
+// GC per-sample scalar outputs (the index outputs may be NULL).
+struct GcScalars {
+  int64_t *idxs = nullptr, *vg = nullptr, *ag = nullptr;
+  double *masks = nullptr, *rewards = nullptr;
+};
+
+// ------------------------------------------------------------------ launches
+// The only launch site of each kernel: the one-shot entry points and the
+// sampler plan both come through here.  flat4 = flat4_columns() of the table.
+static ogbx_status launch_gc_sample(const ogbx_gc_buffer& buf, const ogbx_gc_config& cfg, const GcParams& pr,
+                                    const GcColumns& cc, int32_t num_cols, bool flat4, int64_t total,
+                                    uint64_t call, const ogbx_gc_draws& dr, const ogbx_gc_draw_record& rec,
+                                    const GcScalars& o, hipStream_t s) {
+  const int64_t tile = gc_tile(total), blocks = (total + tile - 1) / tile;
+  const auto kern = any_draw(dr) ? gc_sample_kernel<true> : gc_sample_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, s, buf, cfg, cc, num_cols, total, (int)tile, dr,
+                     pr.k0, pr.k1, (uint32_t)call, (uint32_t)(call >> 32), pr.v_log_q, pr.a_log_q, o.idxs, o.vg,
+                     o.ag, o.masks, o.rewards, rec, tile <= 4 && flat4);
+  OGBX_LAUNCHED("gc_sample_kernel");
+  return OGBX_OK;
+}
+
+static ogbx_status launch_hgc_sample(const ogbx_gc_buffer& buf, const ogbx_gc_config& cfg,
+                                     const ogbx_hgc_config& hcfg, const GcParams& pr, const GcColumns& cc,
+                                     int32_t num_cols, bool flat4, int64_t total, uint64_t call,
+                                     const ogbx_hgc_draws& dr, const ogbx_hgc_draw_record& rec,
+                                     const ogbx_hgc_outputs& o, hipStream_t s) {
+  const int64_t tile = gc_tile(total), blocks = (total + tile - 1) / tile;
+  const bool inj = any_draw(dr.gc) || dr.l_pick || dr.l_geom || dr.l_u_traj || dr.l_u_cur;
+  const auto kern = inj ? hgc_sample_kernel<true> : hgc_sample_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, s, buf, cfg, hcfg, cc, num_cols, total, (int)tile,
+                     dr, pr.k0, pr.k1, (uint32_t)call, (uint32_t)(call >> 32), pr.v_log_q, pr.a_log_q, pr.l_log_q,
+                     o, rec, tile <= 4 && flat4);
+  OGBX_LAUNCHED("hgc_sample_kernel");
+  return OGBX_OK;
+}
+
+// Cols: GcColumns, or a plan's GcColumnsSmall image of at most 16 columns.
+// One workgroup per sample; `call + 1`'s selectors go to ahead_out.
+template <class Cols>
+static ogbx_status launch_gc_ahead(const ogbx_gc_buffer& buf, const ogbx_gc_config& cfg, const GcParams& pr,
+                                   const Cols& cols, int32_t num_cols, bool flat4, int64_t total, uint64_t call,
+                                   const int64_t* ahead_in, int64_t* ahead_out, const GcScalars& o,
+                                   hipStream_t s) {
+  const uint64_t next = call + 1;
+  const auto kern = ahead_in ? gc_ahead_kernel<true, Cols> : gc_ahead_kernel<false, Cols>;
+  hipLaunchKernelGGL(kern, dim3((uint32_t)total), dim3(256), 0, s, buf, cfg, cols, num_cols, pr.k0, pr.k1,
+                     (uint32_t)call, (uint32_t)(call >> 32), (uint32_t)next, (uint32_t)(next >> 32), pr.v_log_q,
+                     pr.a_log_q, ahead_in, ahead_out, o.idxs, o.vg, o.ag, o.masks, o.rewards, flat4);
+  OGBX_LAUNCHED("gc_ahead_kernel");
+  return OGBX_OK;
+}
+
+template <class Cols>
+static ogbx_status launch_hgc_ahead(const ogbx_gc_buffer& buf, const ogbx_gc_config& cfg,
+                                    const ogbx_hgc_config& hcfg, const GcParams& pr, const Cols& cols,
+                                    int32_t num_cols, bool flat4, int64_t total, uint64_t call,
+                                    const int64_t* ahead_in, int64_t* ahead_out, const ogbx_hgc_outputs& o,
+                                    hipStream_t s) {
+  const uint64_t next = call + 1;
+  const auto kern = ahead_in ? hgc_ahead_kernel<true, Cols> : hgc_ahead_kernel<false, Cols>;
+  hipLaunchKernelGGL(kern, dim3((uint32_t)total), dim3(256), 0, s, buf, cfg, hcfg, cols, num_cols, pr.k0, pr.k1,
+                     (uint32_t)call, (uint32_t)(call >> 32), (uint32_t)next, (uint32_t)(next >> 32), pr.v_log_q,
+                     pr.a_log_q, pr.l_log_q, ahead_in, ahead_out, o, flat4);
+  OGBX_LAUNCHED("hgc_ahead_kernel");
+  return OGBX_OK;
+}
+
 extern "C" {
 
 ogbx_status ogbx_gc_sample(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg,
@@ -965,47 +1118,15 @@ ogbx_status ogbx_gc_sample(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg,
                            uint64_t call_index, int64_t* idxs_out, int64_t* value_goal_out,
                            int64_t* actor_goal_out, double* masks, double* rewards,
                            const ogbx_gc_draw_record* record, void* stream) {
-  OGBX_CHECK(buf && cfg && masks && rewards, OGBX_EINVAL, "ogbx_gc_sample: null argument");
-  OGBX_CHECK(num_cols >= 0 && num_cols <= kGcMaxCols, OGBX_EINVAL,
-             "ogbx_gc_sample: at most 32 columns");
-  OGBX_CHECK(batch > 0 && num_batches > 0, OGBX_EINVAL, "batch and num_batches must be > 0");
-  OGBX_CHECK(buf->num_rows > 0 && buf->traj_end, OGBX_EINVAL, "empty trajectory buffer");
-  OGBX_CHECK(buf->valid_idxs == nullptr || buf->num_valid > 0, OGBX_EINVAL,
-             "no valid transitions in the dataset");
-  OGBX_CHECK(periodic_ok(*buf), OGBX_EINVAL, "ogbx_gc_buffer: inconsistent period fields");
+  const char* who = "ogbx_gc_sample";
+  OGBX_CHECK(buf && cfg && masks && rewards, OGBX_EINVAL, named(who, "null argument"));
   GcColumns cc{};
-  for (int i = 0; i < num_cols; ++i) {
-    OGBX_CHECK(cols[i].src_stride == 0 || cols[i].src_stride >= cols[i].row_bytes, OGBX_EINVAL,
-               "ogbx_gc_sample: src_stride below row_bytes");
-    OGBX_CHECK(cols[i].src && cols[i].dst && cols[i].row_bytes > 0 && cols[i].select >= 0 &&
-                   cols[i].select <= 3,
-               OGBX_EINVAL, "ogbx_gc_sample: bad column descriptor");
-    cc.c[i] = cols[i];
-  }
-  ogbx_gc_draws dr{};
-  if (draws) dr = *draws;
-  ogbx_gc_draw_record rec{};
-  if (record) rec = *record;
-  const int64_t total = batch * num_batches;
-  // tile: one sample per workgroup up to 1024 samples (B = 1024: 1,024
-  // workgroups of 256 threads; measured against 2 and 4 samples per workgroup
-  // and 64- to 1024-thread workgroups), then up to 64 per workgroup
-  int64_t tile = total / 1024;
-  if (tile < 1) tile = 1;
-  if (tile > kGcMaxTile) tile = kGcMaxTile;
-  const int64_t blocks = (total + tile - 1) / tile;
-  uint32_t k0, k1;
-  seed_key(seed, kTagGcSample, &k0, &k1);
-  const double v_log_q = std::log(1.0 - (1.0 - cfg->value_discount));
-  const double a_log_q = std::log(1.0 - (1.0 - cfg->actor_discount));
-  auto kern = any_draw(dr) ? gc_sample_kernel<true> : gc_sample_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream,
-                     *buf, *cfg, cc, num_cols, total, (int)tile, dr, k0, k1,
-                     (uint32_t)call_index, (uint32_t)(call_index >> 32), v_log_q, a_log_q,
-                     idxs_out, value_goal_out, actor_goal_out, masks, rewards, rec,
-                     tile <= 4 && flat4_columns(cc, num_cols));
-  OGBX_LAUNCHED("gc_sample_kernel");
-  return OGBX_OK;
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, 3, who, &cc));
+  GC_TRY(check_buffer(buf));
+  return launch_gc_sample(*buf, *cfg, gc_params(seed, *cfg, nullptr), cc, num_cols, flat4_columns(cc, num_cols),
+                          batch * num_batches, call_index, draws ? *draws : ogbx_gc_draws{},
+                          record ? *record : ogbx_gc_draw_record{},
+                          {idxs_out, value_goal_out, actor_goal_out, masks, rewards}, (hipStream_t)stream);
 }
 
 ogbx_status ogbx_gc_sample_ahead(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg,
@@ -1014,37 +1135,15 @@ ogbx_status ogbx_gc_sample_ahead(const ogbx_gc_buffer* buf, const ogbx_gc_config
                                  const int64_t* ahead_in, int64_t* ahead_out, int64_t* idxs_out,
                                  int64_t* value_goal_out, int64_t* actor_goal_out, double* masks,
                                  double* rewards, void* stream) {
-  OGBX_CHECK(buf && cfg && masks && rewards, OGBX_EINVAL, "ogbx_gc_sample_ahead: null argument");
-  OGBX_CHECK(num_cols >= 0 && num_cols <= kGcMaxCols, OGBX_EINVAL, "ogbx_gc_sample_ahead: at most 32 columns");
-  OGBX_CHECK(batch > 0 && num_batches > 0, OGBX_EINVAL, "batch and num_batches must be > 0");
-  const int64_t total = batch * num_batches;
-  OGBX_CHECK(total <= kGcAheadMaxSamples, OGBX_EINVAL,
-             "ogbx_gc_sample_ahead: at most 1024 samples per call (one per workgroup)");
-  OGBX_CHECK(buf->num_rows > 0 && buf->traj_end, OGBX_EINVAL, "empty trajectory buffer");
-  OGBX_CHECK(buf->valid_idxs == nullptr || buf->num_valid > 0, OGBX_EINVAL, "no valid transitions in the dataset");
-  OGBX_CHECK(periodic_ok(*buf), OGBX_EINVAL, "ogbx_gc_buffer: inconsistent period fields");
-  OGBX_CHECK(ahead_in != ahead_out || ahead_in == nullptr, OGBX_EINVAL,
-             "ogbx_gc_sample_ahead: ahead_in and ahead_out must differ");
+  const char* who = "ogbx_gc_sample_ahead";
+  OGBX_CHECK(buf && cfg && masks && rewards, OGBX_EINVAL, named(who, "null argument"));
   GcColumns cc{};
-  for (int i = 0; i < num_cols; ++i) {
-    OGBX_CHECK(cols[i].src_stride == 0 || cols[i].src_stride >= cols[i].row_bytes, OGBX_EINVAL,
-               "ogbx_gc_sample_ahead: src_stride below row_bytes");
-    OGBX_CHECK(cols[i].src && cols[i].dst && cols[i].row_bytes > 0 && cols[i].select >= 0 && cols[i].select <= 3,
-               OGBX_EINVAL, "ogbx_gc_sample_ahead: bad column descriptor");
-    cc.c[i] = cols[i];
-  }
-  uint32_t k0, k1;
-  seed_key(seed, kTagGcSample, &k0, &k1);
-  const double v_log_q = std::log(1.0 - (1.0 - cfg->value_discount));
-  const double a_log_q = std::log(1.0 - (1.0 - cfg->actor_discount));
-  const uint64_t next = call_index + 1;
-  const auto kern = ahead_in ? gc_ahead_kernel<true> : gc_ahead_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((uint32_t)total), dim3(256), 0, (hipStream_t)stream, *buf, *cfg, cc,
-                     num_cols, k0, k1, (uint32_t)call_index, (uint32_t)(call_index >> 32), (uint32_t)next,
-                     (uint32_t)(next >> 32), v_log_q, a_log_q, ahead_in, ahead_out, idxs_out, value_goal_out,
-                     actor_goal_out, masks, rewards, flat4_columns(cc, num_cols));
-  OGBX_LAUNCHED("gc_ahead_kernel");
-  return OGBX_OK;
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, 3, who, &cc));
+  GC_TRY(check_ahead(batch * num_batches, ahead_in, ahead_out, who));
+  GC_TRY(check_buffer(buf));
+  return launch_gc_ahead(*buf, *cfg, gc_params(seed, *cfg, nullptr), cc, num_cols, flat4_columns(cc, num_cols),
+                         batch * num_batches, call_index, ahead_in, ahead_out,
+                         {idxs_out, value_goal_out, actor_goal_out, masks, rewards}, (hipStream_t)stream);
 }
 
 ogbx_status ogbx_hgc_sample(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg,
@@ -1053,54 +1152,17 @@ ogbx_status ogbx_hgc_sample(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg
                             const ogbx_hgc_draws* draws, uint64_t seed, uint64_t call_index,
                             const ogbx_hgc_outputs* out, const ogbx_hgc_draw_record* record,
                             void* stream) {
-  OGBX_CHECK(buf && cfg && hcfg && out, OGBX_EINVAL, "ogbx_hgc_sample: null argument");
-  OGBX_CHECK(out->high_value_offsets && out->high_value_subgoal_steps && out->high_value_masks &&
-                 out->high_value_rewards && out->low_value_subgoal_steps && out->low_value_masks &&
-                 out->low_value_rewards && out->masks && out->rewards,
-             OGBX_EINVAL, "ogbx_hgc_sample: missing scalar output");
-  OGBX_CHECK(hcfg->hv_mask_table && hcfg->hv_reward_table && hcfg->lv_mask_table && hcfg->lv_reward_table,
-             OGBX_EINVAL, "ogbx_hgc_sample: missing reward/mask tables");
-  OGBX_CHECK(hcfg->value_subgoal_steps >= 0 && hcfg->low_subgoal_steps >= 0 && hcfg->actor_subgoal_steps >= 0,
-             OGBX_EINVAL, "ogbx_hgc_sample: negative subgoal steps");
-  OGBX_CHECK(!hcfg->has_low_value_goals || (hcfg->low_discount > 0.0 && hcfg->low_discount < 1.0),
-             OGBX_EINVAL, "ogbx_hgc_sample: low_discount must be in (0, 1)");
-  OGBX_CHECK(num_cols >= 0 && num_cols <= kGcMaxCols, OGBX_EINVAL, "ogbx_hgc_sample: at most 32 columns");
-  OGBX_CHECK(batch > 0 && num_batches > 0, OGBX_EINVAL, "batch and num_batches must be > 0");
-  OGBX_CHECK(buf->num_rows > 0 && buf->traj_end, OGBX_EINVAL, "empty trajectory buffer");
-  OGBX_CHECK(buf->valid_idxs == nullptr || buf->num_valid > 0, OGBX_EINVAL,
-             "no valid transitions in the dataset");
-  OGBX_CHECK(periodic_ok(*buf), OGBX_EINVAL, "ogbx_gc_buffer: inconsistent period fields");
+  const char* who = "ogbx_hgc_sample";
+  OGBX_CHECK(buf && cfg && hcfg && out, OGBX_EINVAL, named(who, "null argument"));
   GcColumns cc{};
-  for (int i = 0; i < num_cols; ++i) {
-    OGBX_CHECK(cols[i].src_stride == 0 || cols[i].src_stride >= cols[i].row_bytes, OGBX_EINVAL,
-               "ogbx_gc_sample: src_stride below row_bytes");
-    OGBX_CHECK(cols[i].src && cols[i].dst && cols[i].row_bytes > 0 && cols[i].select >= 0 &&
-                   cols[i].select < kHgcSel,
-               OGBX_EINVAL, "ogbx_hgc_sample: bad column descriptor");
-    cc.c[i] = cols[i];
-  }
-  ogbx_hgc_draws dr{};
-  if (draws) dr = *draws;
-  ogbx_hgc_draw_record rec{};
-  if (record) rec = *record;
-  const int64_t total = batch * num_batches;
-  int64_t tile = total / 1024;  // as ogbx_gc_sample
-  if (tile < 1) tile = 1;
-  if (tile > kGcMaxTile) tile = kGcMaxTile;
-  const int64_t blocks = (total + tile - 1) / tile;
-  uint32_t k0, k1;
-  seed_key(seed, kTagHgcSample, &k0, &k1);
-  const double v_log_q = std::log(1.0 - (1.0 - cfg->value_discount));
-  const double a_log_q = std::log(1.0 - (1.0 - cfg->actor_discount));
-  const double l_log_q = hcfg->has_low_value_goals ? std::log(1.0 - (1.0 - hcfg->low_discount)) : 0.0;
-  const bool inj = any_draw(dr.gc) || dr.l_pick || dr.l_geom || dr.l_u_traj || dr.l_u_cur;
-  auto kern = inj ? hgc_sample_kernel<true> : hgc_sample_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, *buf,
-                     *cfg, *hcfg, cc, num_cols, total, (int)tile, dr, k0, k1, (uint32_t)call_index,
-                     (uint32_t)(call_index >> 32), v_log_q, a_log_q, l_log_q, *out, rec,
-                     tile <= 4 && flat4_columns(cc, num_cols));
-  OGBX_LAUNCHED("hgc_sample_kernel");
-  return OGBX_OK;
+  GC_TRY(check_hgc_outputs(out, who));
+  GC_TRY(check_hgc_config(hcfg, who));
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, kHgcSel - 1, who, &cc));
+  GC_TRY(check_buffer(buf));
+  return launch_hgc_sample(*buf, *cfg, *hcfg, gc_params(seed, *cfg, hcfg), cc, num_cols,
+                           flat4_columns(cc, num_cols), batch * num_batches, call_index,
+                           draws ? *draws : ogbx_hgc_draws{}, record ? *record : ogbx_hgc_draw_record{}, *out,
+                           (hipStream_t)stream);
 }
 
 ogbx_status ogbx_hgc_sample_ahead(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg,
@@ -1108,49 +1170,17 @@ ogbx_status ogbx_hgc_sample_ahead(const ogbx_gc_buffer* buf, const ogbx_gc_confi
                                   int64_t batch, int64_t num_batches, uint64_t seed, uint64_t call_index,
                                   const int64_t* ahead_in, int64_t* ahead_out, const ogbx_hgc_outputs* out,
                                   void* stream) {
-  OGBX_CHECK(buf && cfg && hcfg && out, OGBX_EINVAL, "ogbx_hgc_sample_ahead: null argument");
-  OGBX_CHECK(out->high_value_offsets && out->high_value_subgoal_steps && out->high_value_masks &&
-                 out->high_value_rewards && out->low_value_subgoal_steps && out->low_value_masks &&
-                 out->low_value_rewards && out->masks && out->rewards,
-             OGBX_EINVAL, "ogbx_hgc_sample_ahead: missing scalar output");
-  OGBX_CHECK(hcfg->hv_mask_table && hcfg->hv_reward_table && hcfg->lv_mask_table && hcfg->lv_reward_table,
-             OGBX_EINVAL, "ogbx_hgc_sample_ahead: missing reward/mask tables");
-  OGBX_CHECK(hcfg->value_subgoal_steps >= 0 && hcfg->low_subgoal_steps >= 0 && hcfg->actor_subgoal_steps >= 0,
-             OGBX_EINVAL, "ogbx_hgc_sample_ahead: negative subgoal steps");
-  OGBX_CHECK(!hcfg->has_low_value_goals || (hcfg->low_discount > 0.0 && hcfg->low_discount < 1.0), OGBX_EINVAL,
-             "ogbx_hgc_sample_ahead: low_discount must be in (0, 1)");
-  OGBX_CHECK(num_cols >= 0 && num_cols <= kGcMaxCols, OGBX_EINVAL, "ogbx_hgc_sample_ahead: at most 32 columns");
-  OGBX_CHECK(batch > 0 && num_batches > 0, OGBX_EINVAL, "batch and num_batches must be > 0");
-  const int64_t total = batch * num_batches;
-  OGBX_CHECK(total <= kGcAheadMaxSamples, OGBX_EINVAL,
-             "ogbx_hgc_sample_ahead: at most 1024 samples per call (one per workgroup)");
-  OGBX_CHECK(buf->num_rows > 0 && buf->traj_end, OGBX_EINVAL, "empty trajectory buffer");
-  OGBX_CHECK(buf->valid_idxs == nullptr || buf->num_valid > 0, OGBX_EINVAL, "no valid transitions in the dataset");
-  OGBX_CHECK(periodic_ok(*buf), OGBX_EINVAL, "ogbx_gc_buffer: inconsistent period fields");
-  OGBX_CHECK(ahead_in != ahead_out || ahead_in == nullptr, OGBX_EINVAL,
-             "ogbx_hgc_sample_ahead: ahead_in and ahead_out must differ");
+  const char* who = "ogbx_hgc_sample_ahead";
+  OGBX_CHECK(buf && cfg && hcfg && out, OGBX_EINVAL, named(who, "null argument"));
   GcColumns cc{};
-  for (int i = 0; i < num_cols; ++i) {
-    OGBX_CHECK(cols[i].src_stride == 0 || cols[i].src_stride >= cols[i].row_bytes, OGBX_EINVAL,
-               "ogbx_hgc_sample_ahead: src_stride below row_bytes");
-    OGBX_CHECK(cols[i].src && cols[i].dst && cols[i].row_bytes > 0 && cols[i].select >= 0 &&
-                   cols[i].select < kHgcSel,
-               OGBX_EINVAL, "ogbx_hgc_sample_ahead: bad column descriptor");
-    cc.c[i] = cols[i];
-  }
-  uint32_t k0, k1;
-  seed_key(seed, kTagHgcSample, &k0, &k1);
-  const double v_log_q = std::log(1.0 - (1.0 - cfg->value_discount));
-  const double a_log_q = std::log(1.0 - (1.0 - cfg->actor_discount));
-  const double l_log_q = hcfg->has_low_value_goals ? std::log(1.0 - (1.0 - hcfg->low_discount)) : 0.0;
-  const uint64_t next = call_index + 1;
-  const auto kern = ahead_in ? hgc_ahead_kernel<true> : hgc_ahead_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((uint32_t)total), dim3(256), 0, (hipStream_t)stream, *buf, *cfg, *hcfg,
-                     cc, num_cols, k0, k1, (uint32_t)call_index, (uint32_t)(call_index >> 32), (uint32_t)next,
-                     (uint32_t)(next >> 32), v_log_q, a_log_q, l_log_q, ahead_in, ahead_out, *out,
-                     flat4_columns(cc, num_cols));
-  OGBX_LAUNCHED("hgc_ahead_kernel");
-  return OGBX_OK;
+  GC_TRY(check_hgc_outputs(out, who));
+  GC_TRY(check_hgc_config(hcfg, who));
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, kHgcSel - 1, who, &cc));
+  GC_TRY(check_ahead(batch * num_batches, ahead_in, ahead_out, who));
+  GC_TRY(check_buffer(buf));
+  return launch_hgc_ahead(*buf, *cfg, *hcfg, gc_params(seed, *cfg, hcfg), cc, num_cols,
+                          flat4_columns(cc, num_cols), batch * num_batches, call_index, ahead_in, ahead_out, *out,
+                          (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -1170,9 +1200,8 @@ struct PlanBatch {
   bool set = false;
   GcColumns cc{};
   int32_t ncols = 0;
-  int64_t batch = 0, nb = 0;
-  int64_t *idxs = nullptr, *vg = nullptr, *ag = nullptr;
-  double *masks = nullptr, *rewards = nullptr;
+  int64_t total = 0;  // batch * num_batches
+  GcScalars out{};
   ogbx_hgc_outputs hout{};
   bool flat4 = false;
   bool small = false;  // ncols <= kGcSmallCols: launch with cs
@@ -1191,8 +1220,7 @@ struct ogbx_gc_plan_s {
   ogbx_hgc_config hcfg;
   bool hgc = false, lookahead = true;
   int device = 0;
-  uint32_t k0 = 0, k1 = 0;
-  double v_log_q = 0, a_log_q = 0, l_log_q = 0;
+  GcParams pr;
   PlanBatch slots[OGBX_GC_PLAN_SLOTS];
   PlanPair pairs[kPlanStreams];
   int npairs = 0;
@@ -1212,18 +1240,10 @@ extern "C" {
 ogbx_status ogbx_gc_plan_create(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg,
                                 const ogbx_hgc_config* hcfg, uint64_t seed, int32_t lookahead,
                                 ogbx_gc_plan_t* plan) {
-  OGBX_CHECK(buf && cfg && plan, OGBX_EINVAL, "ogbx_gc_plan_create: null argument");
-  OGBX_CHECK(buf->num_rows > 0 && buf->traj_end, OGBX_EINVAL, "empty trajectory buffer");
-  OGBX_CHECK(buf->valid_idxs == nullptr || buf->num_valid > 0, OGBX_EINVAL, "no valid transitions in the dataset");
-  OGBX_CHECK(periodic_ok(*buf), OGBX_EINVAL, "ogbx_gc_buffer: inconsistent period fields");
-  if (hcfg) {
-    OGBX_CHECK(hcfg->hv_mask_table && hcfg->hv_reward_table && hcfg->lv_mask_table && hcfg->lv_reward_table,
-               OGBX_EINVAL, "ogbx_gc_plan_create: missing reward/mask tables");
-    OGBX_CHECK(hcfg->value_subgoal_steps >= 0 && hcfg->low_subgoal_steps >= 0 && hcfg->actor_subgoal_steps >= 0,
-               OGBX_EINVAL, "ogbx_gc_plan_create: negative subgoal steps");
-    OGBX_CHECK(!hcfg->has_low_value_goals || (hcfg->low_discount > 0.0 && hcfg->low_discount < 1.0), OGBX_EINVAL,
-               "ogbx_gc_plan_create: low_discount must be in (0, 1)");
-  }
+  const char* who = "ogbx_gc_plan_create";
+  OGBX_CHECK(buf && cfg && plan, OGBX_EINVAL, named(who, "null argument"));
+  GC_TRY(check_buffer(buf));
+  if (hcfg) GC_TRY(check_hgc_config(hcfg, who));
   auto* p = new (std::nothrow) ogbx_gc_plan_s();
   OGBX_CHECK(p, OGBX_ENOMEM, "ogbx_gc_plan_create: out of host memory");
   p->buf = *buf;
@@ -1238,10 +1258,7 @@ ogbx_status ogbx_gc_plan_create(const ogbx_gc_buffer* buf, const ogbx_gc_config*
     p->device = attr.device;
   else if (hipGetDevice(&p->device) != hipSuccess)
     p->device = 0;
-  seed_key(seed, p->hgc ? kTagHgcSample : kTagGcSample, &p->k0, &p->k1);
-  p->v_log_q = std::log(1.0 - (1.0 - cfg->value_discount));
-  p->a_log_q = std::log(1.0 - (1.0 - cfg->actor_discount));
-  p->l_log_q = (hcfg && hcfg->has_low_value_goals) ? std::log(1.0 - (1.0 - hcfg->low_discount)) : 0.0;
+  p->pr = gc_params(seed, *cfg, hcfg);
   *plan = p;
   return OGBX_OK;
 }
@@ -1250,36 +1267,18 @@ ogbx_status ogbx_gc_plan_set_batch(ogbx_gc_plan_t p, int32_t slot, const ogbx_gc
                                    int64_t batch, int64_t num_batches, int64_t* idxs_out, int64_t* value_goal_out,
                                    int64_t* actor_goal_out, double* masks, double* rewards,
                                    const ogbx_hgc_outputs* hgc_out) {
+  const char* who = "ogbx_gc_plan_set_batch";
   OGBX_CHECK(p, OGBX_EINVAL, "null plan");
-  OGBX_CHECK(slot >= 0 && slot < OGBX_GC_PLAN_SLOTS, OGBX_EINVAL, "ogbx_gc_plan_set_batch: slot out of range");
-  OGBX_CHECK(num_cols >= 0 && num_cols <= kGcMaxCols, OGBX_EINVAL, "ogbx_gc_plan_set_batch: at most 32 columns");
-  OGBX_CHECK(batch > 0 && num_batches > 0, OGBX_EINVAL, "batch and num_batches must be > 0");
-  if (p->hgc) {
-    OGBX_CHECK(hgc_out && hgc_out->high_value_offsets && hgc_out->high_value_subgoal_steps &&
-                   hgc_out->high_value_masks && hgc_out->high_value_rewards && hgc_out->low_value_subgoal_steps &&
-                   hgc_out->low_value_masks && hgc_out->low_value_rewards && hgc_out->masks && hgc_out->rewards,
-               OGBX_EINVAL, "ogbx_gc_plan_set_batch: missing HGC scalar output");
-  } else {
-    OGBX_CHECK(masks && rewards, OGBX_EINVAL, "ogbx_gc_plan_set_batch: null masks / rewards");
-  }
+  OGBX_CHECK(slot >= 0 && slot < OGBX_GC_PLAN_SLOTS, OGBX_EINVAL, named(who, "slot out of range"));
   PlanBatch b;
-  const int max_sel = p->hgc ? kHgcSel - 1 : 3;
-  for (int i = 0; i < num_cols; ++i) {
-    OGBX_CHECK(cols[i].src_stride == 0 || cols[i].src_stride >= cols[i].row_bytes, OGBX_EINVAL,
-               "ogbx_gc_plan_set_batch: src_stride below row_bytes");
-    OGBX_CHECK(cols[i].src && cols[i].dst && cols[i].row_bytes > 0 && cols[i].select >= 0 &&
-                   cols[i].select <= max_sel,
-               OGBX_EINVAL, "ogbx_gc_plan_set_batch: bad column descriptor");
-    b.cc.c[i] = cols[i];
-  }
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, p->hgc ? kHgcSel - 1 : 3, who, &b.cc));
+  if (p->hgc)
+    GC_TRY(check_hgc_outputs(hgc_out, who));
+  else
+    OGBX_CHECK(masks && rewards, OGBX_EINVAL, named(who, "null masks / rewards"));
   b.ncols = num_cols;
-  b.batch = batch;
-  b.nb = num_batches;
-  b.idxs = idxs_out;
-  b.vg = value_goal_out;
-  b.ag = actor_goal_out;
-  b.masks = masks;
-  b.rewards = rewards;
+  b.total = batch * num_batches;
+  b.out = {idxs_out, value_goal_out, actor_goal_out, masks, rewards};
   if (hgc_out) b.hout = *hgc_out;
   b.flat4 = flat4_columns(b.cc, num_cols);
   b.small = num_cols <= kGcSmallCols;
@@ -1296,28 +1295,15 @@ ogbx_status ogbx_gc_plan_sample(ogbx_gc_plan_t p, int32_t slot, uint64_t call_in
   OGBX_CHECK(slot >= 0 && slot < OGBX_GC_PLAN_SLOTS && p->slots[slot].set, OGBX_EINVAL,
              "ogbx_gc_plan_sample: no batch in this slot");
   const PlanBatch& b = p->slots[slot];
-  const int64_t total = b.batch * b.nb;
+  const int64_t total = b.total;
   hipStream_t s = (hipStream_t)stream;
-  const uint32_t clo = (uint32_t)call_index, chi = (uint32_t)(call_index >> 32);
   if (!p->lookahead || total > kGcAheadMaxSamples) {
     p->key_valid = false;
-    int64_t tile = total / 1024;  // as ogbx_gc_sample
-    if (tile < 1) tile = 1;
-    if (tile > kGcMaxTile) tile = kGcMaxTile;
-    const int64_t blocks = (total + tile - 1) / tile;
-    const bool f4 = tile <= 4 && b.flat4;
-    if (p->hgc) {
-      hipLaunchKernelGGL(hgc_sample_kernel<false>, dim3((uint32_t)blocks), dim3(256), 0, s, p->buf, p->cfg, p->hcfg,
-                         b.cc, b.ncols, total, (int)tile, ogbx_hgc_draws{}, p->k0, p->k1, clo, chi, p->v_log_q,
-                         p->a_log_q, p->l_log_q, b.hout, ogbx_hgc_draw_record{}, f4);
-      OGBX_LAUNCHED("hgc_sample_kernel");
-    } else {
-      hipLaunchKernelGGL(gc_sample_kernel<false>, dim3((uint32_t)blocks), dim3(256), 0, s, p->buf, p->cfg, b.cc,
-                         b.ncols, total, (int)tile, ogbx_gc_draws{}, p->k0, p->k1, clo, chi, p->v_log_q, p->a_log_q,
-                         b.idxs, b.vg, b.ag, b.masks, b.rewards, ogbx_gc_draw_record{}, f4);
-      OGBX_LAUNCHED("gc_sample_kernel");
-    }
-    return OGBX_OK;
+    if (p->hgc)
+      return launch_hgc_sample(p->buf, p->cfg, p->hcfg, p->pr, b.cc, b.ncols, b.flat4, total, call_index,
+                               ogbx_hgc_draws{}, ogbx_hgc_draw_record{}, b.hout, s);
+    return launch_gc_sample(p->buf, p->cfg, p->pr, b.cc, b.ncols, b.flat4, total, call_index, ogbx_gc_draws{},
+                            ogbx_gc_draw_record{}, b.out, s);
   }
   // this stream's buffer pair (allocated on its first call; with every pair
   // taken, the call runs without look-ahead: nothing stored, nothing read)
@@ -1353,31 +1339,18 @@ ogbx_status ogbx_gc_plan_sample(ogbx_gc_plan_t p, int32_t slot, uint64_t call_in
     }
     out = p->pairs[pi].buf[which];
   }
-  const uint64_t next = call_index + 1;
   auto launch = [&](const auto& cols) {
-    using C = std::decay_t<decltype(cols)>;
-    if (p->hgc) {
-      const auto kern = in ? hgc_ahead_kernel<true, C> : hgc_ahead_kernel<false, C>;
-      hipLaunchKernelGGL(kern, dim3((uint32_t)total), dim3(256), 0, s, p->buf, p->cfg, p->hcfg, cols, b.ncols, p->k0,
-                         p->k1, clo, chi, (uint32_t)next, (uint32_t)(next >> 32), p->v_log_q, p->a_log_q, p->l_log_q,
-                         in, out, b.hout, b.flat4);
-    } else {
-      const auto kern = in ? gc_ahead_kernel<true, C> : gc_ahead_kernel<false, C>;
-      hipLaunchKernelGGL(kern, dim3((uint32_t)total), dim3(256), 0, s, p->buf, p->cfg, cols, b.ncols, p->k0, p->k1,
-                         clo, chi, (uint32_t)next, (uint32_t)(next >> 32), p->v_log_q, p->a_log_q, in, out, b.idxs,
-                         b.vg, b.ag, b.masks, b.rewards, b.flat4);
-    }
+    if (p->hgc)
+      return launch_hgc_ahead(p->buf, p->cfg, p->hcfg, p->pr, cols, b.ncols, b.flat4, total, call_index, in, out,
+                              b.hout, s);
+    return launch_gc_ahead(p->buf, p->cfg, p->pr, cols, b.ncols, b.flat4, total, call_index, in, out, b.out, s);
   };
-  if (b.small)
-    launch(b.cs);
-  else
-    launch(b.cc);
-  OGBX_LAUNCHED(p->hgc ? "hgc_ahead_kernel" : "gc_ahead_kernel");
+  GC_TRY(b.small ? launch(b.cs) : launch(b.cc));
   p->key_valid = pi >= 0;
   p->key_pair = pi;
   p->key_which = which;
   p->key_total = total;
-  p->key_call = next;
+  p->key_call = call_index + 1;
   return OGBX_OK;
 }
 

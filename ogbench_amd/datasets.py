@@ -118,6 +118,9 @@ _DRAW_INT = ('pick', 'v_pick', 'v_geom', 'a_pick', 'a_geom')
 _DRAW_FLOAT = ('v_dist', 'v_u_traj', 'v_u_cur', 'a_dist', 'a_u_traj', 'a_u_cur')
 _DRAW_ORDER = ('pick', 'v_pick', 'v_geom', 'v_dist', 'v_u_traj', 'v_u_cur',
                'a_pick', 'a_geom', 'a_dist', 'a_u_traj', 'a_u_cur')
+# HGCDataset's low-level value goal draws
+_HDRAW_LOW = ('l_pick', 'l_geom', 'l_u_traj', 'l_u_cur')
+_HDRAW_INT = _DRAW_INT + ('l_pick', 'l_geom')
 
 
 class GcDraws(ctypes.Structure):
@@ -299,6 +302,13 @@ class GCDataset:
     interleaved copy of the small columns, ``_row_record``) and lookahead
     (default True: each plain call of <= 1,024 samples also computes the next
     call's selectors, so the next call only gathers; ``ogbx_gc_plan_*``).
+
+    ``sampler.dataset`` may be reassigned and its columns replaced or modified
+    in place: sample() notices (one staleness token, ``_refresh_record``) and
+    batches show the current values.  The trajectory tables (``_buf``,
+    ``traj_end``, ``valid_idxs``) are fixed at construction, as the
+    reference's ``__post_init__`` fixes its own: a new dataset must keep the
+    trajectory layout.
     """
 
     def __init__(self, dataset, config, preprocess_frame_stack=True, seed=None, _plain=False):
@@ -349,6 +359,9 @@ class GCDataset:
         self._plain = _plain
         self._record, self._rec_off, self._rec_stride, self._rec_src = self._row_record(dataset)
         self._rec_index()
+        # staleness token, compared at the top of sample(): the dataset object,
+        # its generation and (_rec_versions) the packed columns' versions
+        self._tok_ds, self._tok_gen = dataset, dataset._gen
 
         def thresh(p_traj, p_cur):
             return p_traj / (1.0 - p_cur) if p_cur != 1.0 else 0.0  # datasets.py:321
@@ -367,11 +380,13 @@ class GCDataset:
         # plan (ogbx_gc_plan_*): the prepared output batches and the look-ahead
         # state live in libogbx, so a steady call is one lookup and one launch
         self._lookahead = bool(config.get('lookahead', self._LOOKAHEAD_DEFAULT))
-        self._p_aug = config.get('p_aug')
-        # the reference draws np.random.rand() < p_aug per call (datasets.py:278);
-        # with p_aug 0 the test can never pass and the draw would only advance
+        # The p_aug rule of every sample() path: one np.random.rand() per call
+        # when p_aug > 0 and not evaluation, else none.  The reference draws
+        # whenever p_aug is not None (impls/utils/datasets.py:278); with
+        # p_aug <= 0 its test can never pass and the draw would only advance
         # numpy's global stream (which this sampler's Philox draws do not
-        # follow), so the steady call skips it
+        # follow), so it is skipped here.
+        self._p_aug = config.get('p_aug')
         self._p_aug_live = self._p_aug is not None and float(self._p_aug) > 0.0
         self._dev_idx = self.device.index
         self._plan_sample = L.ogbx_gc_plan_sample
@@ -431,25 +446,22 @@ class GCDataset:
             rec[:, o:o + rb] = t.reshape(self.size, -1).contiguous().view(torch.uint8)
 
     def _refresh_record(self):
-        """Re-pack the row record if a packed column was modified in place or
-        replaced since it was built (same layout, same record buffer: the
-        cached column descriptors stay valid, except on replacement)."""
+        """The full staleness check, run by sample() when its token moved.  A
+        new dataset object or generation (a column was replaced, packed or
+        not) drops the prepared batches: their descriptors hold the old
+        columns' pointers.  A packed column that was replaced or modified in
+        place is re-packed (same layout, same record buffer)."""
         ds = self.dataset
-        # fast check (every sample() call): the packed columns are the same
-        # tensor objects with the same version counters
-        gen = getattr(ds, '_gen', None)
-        if (gen is not None and gen == self._rec_gen) or \
-                all(map(operator.is_, map(ds.get, self._rec_keys), self._rec_tensors)):
-            if tuple(map(_VERSION, self._rec_tensors)) == self._rec_versions:
-                self._rec_gen = gen  # verified: the next calls compare the generation only
-                return
+        if not isinstance(ds, Dataset):
+            ds = self.dataset = Dataset(ds)
+        if ds is not self._tok_ds or ds._gen != self._tok_gen:
+            self._out_cache.clear()
         stale = False
         for k, t, _, _, ver in self._rec_src:
             cur = ds.get(k)
             if cur is not t:
                 if cur is None or cur.shape != t.shape or cur.dtype != t.dtype:
                     raise ValueError(f'dataset column {k!r} changed shape or dtype after the sampler was built')
-                self._out_cache.clear()  # the batch descriptors hold the old column pointers
                 stale = True
             elif t._version != ver:
                 stale = True
@@ -458,12 +470,11 @@ class GCDataset:
             self._fill_record(self._record, src)
             self._rec_src = tuple((k, t, o, rb, t._version) for k, t, o, rb in src)
             self._rec_index()
+        self._tok_ds, self._tok_gen = ds, ds._gen
 
     def _rec_index(self):
-        self._rec_keys = tuple(e[0] for e in self._rec_src)
         self._rec_tensors = tuple(e[1] for e in self._rec_src)
         self._rec_versions = tuple(e[4] for e in self._rec_src)
-        self._rec_gen = None  # set by the next clean check (Dataset._gen of a verified state)
 
     def _column(self, src_key, dst, select):
         """Descriptor of one gathered column (from the row record when the key
@@ -474,13 +485,6 @@ class GCDataset:
         if o is not None:
             return GcColumn(self._record.data_ptr() + o, dst.data_ptr(), row_bytes, select, self._rec_stride)
         return GcColumn(src.data_ptr(), dst.data_ptr(), row_bytes, select, 0)
-
-    def _p_aug_draw(self, out, evaluation):
-        # p_aug draw (datasets.py:278-279): image crops apply only to 4-D arrays
-        p_aug = self.config.get('p_aug')
-        if p_aug is not None and not evaluation:
-            if np.random.rand() < p_aug and any(v.dim() == 4 for v in out.values()):
-                raise NotImplementedError('image augmentation (visual datasets) is out of scope')
 
     def _next_seed(self):
         if self._seed is None:
@@ -550,12 +554,53 @@ class GCDataset:
         self._slot = (slot + 1) % 8  # OGBX_GC_PLAN_SLOTS; the out cache holds at most the last two
         return slot
 
+    # ------------------------------------------ what HGCDataset supplies instead
+    _what = 'gc_sample'  # names the call in error messages
+    _draw_keys = _DRAW_ORDER  # the draws a recording call reports
+
+    def _batch(self, total, keys, record):
+        """A new batch: the output dict, the column descriptors, the scalar
+        outputs as ``_set_batch`` / ``_direct`` pass them on, tensors to keep
+        alive with the batch, and the index keys of a recording call."""
+        torch = _torch()
+        out, cols = self._columns(total, keys)
+        masks = torch.empty(total, dtype=torch.float64, device=self.device)
+        rewards = torch.empty(total, dtype=torch.float64, device=self.device)
+        # index outputs only when asked for (plain sampling or draw recording)
+        idx = torch.empty(total, dtype=torch.int64, device=self.device) if (self._plain or record) else None
+        vg = torch.empty(total, dtype=torch.int64, device=self.device) if record else None
+        ag = torch.empty(total, dtype=torch.int64, device=self.device) if record else None
+        if self._plain:
+            out['_idxs'] = idx
+        else:
+            out['masks'] = masks
+            out['rewards'] = rewards
+        scalars = tuple(map(_lib.ptr, (idx, vg, ag, masks, rewards)))
+        return out, cols, scalars, (masks, rewards), {'_idxs': idx, '_value_goal_idxs': vg, '_actor_goal_idxs': ag}
+
+    def _draw_structs(self):
+        """(injected draws to fill, its GC part)."""
+        dr = GcDraws()
+        return dr, dr
+
+    def _record_struct(self, rec_t):
+        return GcDrawRecord(*[rec_t[k].data_ptr() for k in _DRAW_ORDER])
+
+    def _set_batch(self, plan, slot, col_arr, ncols, B, nb, scalars):
+        return self._L.ogbx_gc_plan_set_batch(plan, slot, col_arr, ncols, B, nb, *scalars, None)
+
+    def _direct(self, col_arr, ncols, B, nb, dr, seed, call, scalars, rec, stream):
+        return self._L.ogbx_gc_sample(self._buf, self._cfg, col_arr, ncols, B, nb, dr, seed, call, *scalars, rec,
+                                      stream)
+
     def sample(self, batch_size, idxs=None, evaluation=False, draws=None, record_draws=False,
                num_batches=1, _keys=None, out=None):
-        """GCDataset.sample (datasets.py:213-294), one fused launch.
+        """GCDataset.sample (datasets.py:213-294) / HGCDataset.sample
+        (datasets.py:496-643), one fused launch.
 
-        draws: optional dict of injected reference draws (see ``_DRAW_ORDER``;
-        device or host arrays of length num_batches*batch_size).
+        draws: optional dict of injected reference draws (see ``_DRAW_ORDER``,
+        for HGCDataset also the low-level ``l_*`` draws; device or host arrays
+        of length num_batches*batch_size).
         record_draws: also return the draws the kernel used (``out['_draws']``).
         num_batches > 1: sample that many independent batches in the same launch
         (outputs have a leading num_batches*batch_size dimension).
@@ -565,102 +610,86 @@ class GCDataset:
         batch) and it is returned.  Skips all per-call allocation.
         """
         plain_call = idxs is None and not draws and not record_draws and _keys is None
-        if self._rec_src:
-            # staleness of the packed row record: a Dataset's generation (no
-            # column replaced since the last verified check) and the packed
-            # columns' version counters; anything else takes the full check
-            gen = getattr(self.dataset, '_gen', None)
-            if (gen is None or gen != self._rec_gen
-                    or tuple(map(_VERSION, self._rec_tensors)) != self._rec_versions):
-                self._refresh_record()
-        if out is not None and plain_call:
-            # the steady refill: one dict lookup, one ctypes call (host time
-            # per call is what bounds sample(1024)'s rate, bench 'extra')
-            hit = self._out_cache.get(id(out))
-            if (hit is not None and hit[0] is out and hit[1] == (batch_size, num_batches)
-                    and self._plan_seed == self._seed):
-                call = self._calls
-                self._calls = call + 1
-                st = self._plan_sample(self._plan, hit[2], call, self._raw_stream(self._dev_idx))
-                if st:
-                    _lib.check(st, 'gc_sample')
-                if self._p_aug_live and not evaluation:
-                    self._p_aug_draw(out, evaluation)
-                return out
+        # the staleness token: the dataset object, its generation (no column
+        # replaced) and the packed columns' version counters (none modified in
+        # place); anything else takes the full check
+        ds = self.dataset
+        if (ds is not self._tok_ds or getattr(ds, '_gen', None) != self._tok_gen
+                or (self._rec_src and tuple(map(_VERSION, self._rec_tensors)) != self._rec_versions)):
+            self._refresh_record()
+        # the steady refill: one dict lookup, one ctypes call (host time per
+        # call is what bounds sample(1024)'s rate, bench 'extra')
+        hit = self._out_cache.get(id(out)) if (out is not None and plain_call) else None
+        if (hit is not None and hit[0] is out and hit[1] == (batch_size, num_batches)
+                and self._plan_seed == self._seed):
+            call = self._calls
+            self._calls = call + 1
+            st = self._plan_sample(self._plan, hit[2], call, self._raw_stream(self._dev_idx))
+            if st:
+                _lib.check(st, self._what)
+            extra = None
+        else:
+            out, extra = self._sample_new(int(batch_size), int(num_batches), idxs, draws, record_draws, _keys,
+                                          plain_call, (batch_size, num_batches))
+        if self._p_aug_live and not evaluation:
+            # image crops apply only to 4-D arrays (datasets.py:278-279)
+            if np.random.rand() < self._p_aug and any(v.dim() == 4 for v in out.values()):
+                raise NotImplementedError('image augmentation (visual datasets) is out of scope')
+        if extra:
+            out.update(extra)
+        return out
+
+    def _sample_new(self, B, nb, idxs, draws, record_draws, keys, plain_call, shape):
+        """A call into a new batch: allocate it, stage idxs / draws, launch
+        through the plan (plain call; the batch's slot is remembered for
+        ``out=``) or the direct entry point.  Returns the batch and the ``_*``
+        keys a recording call adds to it."""
         torch = _torch()
-        total = int(batch_size) * int(num_batches)
-        out, cols = self._columns(total, _keys)
-        col_arr = (GcColumn * max(1, len(cols)))(*cols)
-        masks = torch.empty(total, dtype=torch.float64, device=self.device)
-        rewards = torch.empty(total, dtype=torch.float64, device=self.device)
-        # index outputs only when asked for (plain sampling or draw recording)
-        idx_out = torch.empty(total, dtype=torch.int64, device=self.device) if (self._plain or record_draws) else None
-        vg = torch.empty(total, dtype=torch.int64, device=self.device) if record_draws else None
-        ag = torch.empty(total, dtype=torch.int64, device=self.device) if record_draws else None
-        keep = []
-        dr = GcDraws()
+        total = B * nb
+        out, cols, scalars, keep, idx_t = self._batch(total, keys, record_draws)
+        col_keep = (GcColumn * max(1, len(cols)))(*cols)
+        col_arr = ctypes.cast(col_keep, ctypes.c_void_p)
+        staged = []
+        dr, gdr = self._draw_structs()
         if idxs is not None:
             t = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
             assert t.numel() == total
-            keep.append(t)
-            dr.idxs = t.data_ptr()
-        if draws:
-            for k, v in draws.items():
-                if k == 'idxs':
-                    continue
-                dt = torch.int64 if k in _DRAW_INT else torch.float64
-                t = _to_device(v, self.device).to(dt).reshape(-1)
-                assert t.numel() == total, k
-                keep.append(t)
-                setattr(dr, k, t.data_ptr())
-        rec = None
-        rec_t = None
+            staged.append(t)
+            gdr.idxs = t.data_ptr()
+        for k, v in (draws or {}).items():
+            if k == 'idxs':
+                continue
+            t = _to_device(v, self.device).to(torch.int64 if k in _HDRAW_INT else torch.float64).reshape(-1)
+            assert t.numel() == total, k
+            staged.append(t)
+            setattr(gdr if hasattr(gdr, k) else dr, k, t.data_ptr())
+        rec = rec_t = None
         if record_draws:
-            rec_t = {k: torch.empty(total, dtype=torch.int64 if k in _DRAW_INT else torch.float64,
-                                    device=self.device) for k in _DRAW_ORDER}
-            rec = GcDrawRecord(*[rec_t[k].data_ptr() for k in _DRAW_ORDER])
+            rec_t = {k: torch.empty(total, dtype=torch.int64 if k in _HDRAW_INT else torch.float64,
+                                    device=self.device) for k in self._draw_keys}
+            rec = self._record_struct(rec_t)
         seed, call = self._next_seed()
-        slot = None
+        stream = _lib.stream_of(self.device)
         if plain_call:
             plan = self._plan_for(seed)
             slot = self._next_slot()
-            _lib.check(self._L.ogbx_gc_plan_set_batch(plan, slot, ctypes.cast(col_arr, ctypes.c_void_p), len(cols),
-                                                      int(batch_size), int(num_batches), _lib.ptr(idx_out),
-                                                      _lib.ptr(vg), _lib.ptr(ag), _lib.ptr(masks),
-                                                      _lib.ptr(rewards), None), 'gc_plan_set_batch')
-            st = self._L.ogbx_gc_plan_sample(plan, slot, call, _lib.stream_of(self.device))
-        else:
-            st = self._L.ogbx_gc_sample(
-                self._buf, self._cfg, ctypes.cast(col_arr, ctypes.c_void_p), len(cols), int(batch_size),
-                int(num_batches), dr, seed, call, _lib.ptr(idx_out), _lib.ptr(vg), _lib.ptr(ag), _lib.ptr(masks),
-                _lib.ptr(rewards), rec, _lib.stream_of(self.device))
-        _lib.check(st, 'gc_sample')
-        if self._plain:
-            out['_idxs'] = idx_out
-        else:
-            out['masks'] = masks
-            out['rewards'] = rewards
-        if plain_call:
+            _lib.check(self._set_batch(plan, slot, col_arr, len(cols), B, nb, scalars), 'gc_plan_set_batch')
             # remember the batch's plan slot so that sample(..., out=this) skips
-            # setup (the output tensors stay alive in `out`)
+            # setup (the output tensors stay alive in `out` and `keep`)
             if len(self._out_cache) >= 2:
                 self._out_cache.clear()
-            self._out_cache[id(out)] = (out, (batch_size, num_batches), slot, masks, rewards, idx_out)
-        if self._plain:
-            return out
-        self._p_aug_draw(out, evaluation)
-        if record_draws:
-            out['_draws'] = rec_t
-            out['_idxs'] = idx_out
-            out['_value_goal_idxs'] = vg
-            out['_actor_goal_idxs'] = ag
-        return out
+            self._out_cache[id(out)] = (out, shape, slot, keep)
+            st = self._L.ogbx_gc_plan_sample(plan, slot, call, stream)
+        else:
+            st = self._direct(col_arr, len(cols), B, nb, dr, seed, call, scalars, rec, stream)
+        _lib.check(st, self._what)
+        del staged, col_keep  # alive until the launch was issued
+        if not record_draws or self._plain:
+            return out, None
+        return out, {'_draws': rec_t, **idx_t}
 
 
 # ----------------------------------------------------------------------------- HGCDataset
-
-_HDRAW_LOW = ('l_pick', 'l_geom', 'l_u_traj', 'l_u_cur')
-_HDRAW_INT = _DRAW_INT + ('l_pick', 'l_geom')
 
 
 class HgcConfig(ctypes.Structure):
@@ -748,6 +777,7 @@ class HGCDataset(GCDataset):
         self.actor_subgoal_steps = int(high if c.get('actor_subgoal_steps') is None else c['actor_subgoal_steps'])
         self.low_subgoal_steps = int(c.get('low_subgoal_steps', c['subgoal_steps']))
         self._has_low = c.get('low_discount') is not None
+        self._draw_keys = _DRAW_ORDER + (_HDRAW_LOW if self._has_low else ())
         dev = self.device
         self._hv_tab = _subgoal_tables(c['discount'], self.value_subgoal_steps, c['gc_negative'], dev)
         self._lv_tab = _subgoal_tables(c['discount'], self.low_subgoal_steps, c['gc_negative'], dev)
@@ -804,85 +834,31 @@ class HGCDataset(GCDataset):
         out['low_actor_next_observations'] = col('observations', 9)
         return out, cols
 
-    def sample(self, batch_size, idxs=None, evaluation=False, draws=None, record_draws=False, num_batches=1,
-               out=None):
-        """HGCDataset.sample (datasets.py:496-643), one fused launch.  Arguments
-        as GCDataset.sample; draws may also carry the low-level l_* draws."""
+    # sample() is GCDataset's; what differs for the hierarchical sampler:
+    _what = 'hgc_sample'
+
+    def _batch(self, total, keys, record):
         torch = _torch()
-        total = int(batch_size) * int(num_batches)
-        plain_call = idxs is None and not draws and not record_draws
-        if self._rec_src:
-            # staleness of the packed row record: a Dataset's generation (no
-            # column replaced since the last verified check) and the packed
-            # columns' version counters; anything else takes the full check
-            gen = getattr(self.dataset, '_gen', None)
-            if (gen is None or gen != self._rec_gen
-                    or tuple(map(_VERSION, self._rec_tensors)) != self._rec_versions):
-                self._refresh_record()
-        hit = self._out_cache.get(id(out)) if (out is not None and plain_call) else None
-        if (hit is not None and hit[0] is out and hit[1] == (batch_size, num_batches)
-                and self._plan_seed == self._seed):
-            call = self._calls
-            self._calls = call + 1
-            st = self._plan_sample(self._plan, hit[2], call, self._raw_stream(self._dev_idx))
-            if st:
-                _lib.check(st, 'hgc_sample')
-            if self._p_aug_live and not evaluation:
-                self._p_aug_draw(out, evaluation)
-            return out
-        else:
-            out, cols = self._hcolumns(total)
-            col_keep = (GcColumn * max(1, len(cols)))(*cols)
-            col_arr = ctypes.cast(col_keep, ctypes.c_void_p)
-            ncols = len(cols)
-            ptr = lambda k: out[k].data_ptr() if k in out else None  # noqa: E731
-            outs = HgcOutputs(None, None, None, None, *[ptr(k) for k in _HGC_SCALARS[4:]])
-            keep = []
-            dr = HgcDraws()
-            if idxs is not None:
-                t = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
-                assert t.numel() == total
-                keep.append(t)
-                dr.gc.idxs = t.data_ptr()
-            for k, v in (draws or {}).items():
-                if k == 'idxs':
-                    continue
-                t = _to_device(v, self.device).to(torch.int64 if k in _HDRAW_INT else torch.float64).reshape(-1)
-                assert t.numel() == total, k
-                keep.append(t)
-                setattr(dr.gc if hasattr(dr.gc, k) else dr, k, t.data_ptr())
-            rec = None
-            if record_draws:
-                rec_t = {k: torch.empty(total, dtype=torch.int64 if k in _HDRAW_INT else torch.float64,
-                                        device=self.device) for k in _DRAW_ORDER + _HDRAW_LOW}
-                rec = HgcDrawRecord(GcDrawRecord(*[rec_t[k].data_ptr() for k in _DRAW_ORDER]),
-                                    *[rec_t[k].data_ptr() for k in _HDRAW_LOW])
-                idx_t = {k: torch.empty(total, dtype=torch.int64, device=self.device) for k in _HGC_SCALARS[:4]}
-                for k, t in idx_t.items():
-                    setattr(outs, k, t.data_ptr())
-        seed, call = self._next_seed()
-        stream = _lib.stream_of(self.device)
-        B, nb = int(batch_size), int(num_batches)
-        if plain_call:
-            plan = self._plan_for(seed)
-            slot = self._next_slot()
-            _lib.check(self._Lh.ogbx_gc_plan_set_batch(plan, slot, col_arr, ncols, B, nb, None, None, None, None,
-                                                       None, ctypes.byref(outs)), 'gc_plan_set_batch')
-            if len(self._out_cache) >= 2:
-                self._out_cache.clear()
-            self._out_cache[id(out)] = (out, (batch_size, num_batches), slot, outs, col_keep)
-            st = self._Lh.ogbx_gc_plan_sample(plan, slot, call, stream)
-        else:
-            st = self._Lh.ogbx_hgc_sample(self._buf, self._cfg, self._hcfg, col_arr, ncols, B, nb, dr, seed, call,
-                                          outs, rec, stream)
-        _lib.check(st, 'hgc_sample')
-        self._p_aug_draw(out, evaluation)
-        if record_draws:
-            out['_draws'] = rec_t
-            for k, t in idx_t.items():
-                out['_' + k] = t
-            if not self._has_low:
-                for k in _HDRAW_LOW:
-                    out['_draws'].pop(k)
-        del keep
-        return out
+        assert keys is None
+        out, cols = self._hcolumns(total)
+        idx_t = {k: torch.empty(total, dtype=torch.int64, device=self.device)
+                 for k in (_HGC_SCALARS[:4] if record else ())}
+        outs = HgcOutputs(*[_lib.ptr(idx_t.get(k)) for k in _HGC_SCALARS[:4]],
+                          *[out[k].data_ptr() for k in _HGC_SCALARS[4:]])
+        return out, cols, outs, (), {'_' + k: t for k, t in idx_t.items()}
+
+    def _draw_structs(self):
+        dr = HgcDraws()
+        return dr, dr.gc
+
+    def _record_struct(self, rec_t):
+        # the l_* draws exist (and are recorded) only with low_discount
+        return HgcDrawRecord(super()._record_struct(rec_t), *[_lib.ptr(rec_t.get(k)) for k in _HDRAW_LOW])
+
+    def _set_batch(self, plan, slot, col_arr, ncols, B, nb, outs):
+        return self._Lh.ogbx_gc_plan_set_batch(plan, slot, col_arr, ncols, B, nb, None, None, None, None, None,
+                                               ctypes.byref(outs))
+
+    def _direct(self, col_arr, ncols, B, nb, dr, seed, call, outs, rec, stream):
+        return self._Lh.ogbx_hgc_sample(self._buf, self._cfg, self._hcfg, col_arr, ncols, B, nb, dr, seed, call,
+                                        outs, rec, stream)

@@ -370,3 +370,85 @@ def test_raw_ahead_abi_matches_direct(gpu, gold):
         assert torch.equal(ma, mb) and torch.equal(ra, rb), call
         for k in xa:
             assert torch.equal(xa[k], xb[k]), (call, k)
+
+
+# ---------------------------------------------------------------- one sample()
+# GCDataset and HGCDataset share one sample(): its staleness token and its
+# p_aug rule, checked for both.
+
+def _make_sampler(kind, ds, seed, p_aug=None, **extra):
+    from ogbench_amd.datasets import HGCDataset
+    from test_oracle_hgc import HGC_CONFIGS
+
+    if kind == 'hgc':
+        return HGCDataset(ds, dict(HGC_CONFIGS['hlow'], p_aug=p_aug, **extra), seed=seed)
+    return GCDataset(ds, dict(CONFIGS['gciql'], p_aug=p_aug, frame_stack=None, **extra), seed=seed)
+
+
+@pytest.mark.parametrize('kind', ['gc', 'hgc'])
+def test_reassigned_dataset(gpu, gold, kind):
+    """sampler.dataset = other: two unmodified Datasets have the same
+    generation, so the sampler must compare the object too -- the next batch
+    shows the new dataset's rows, not the packed copy of the old one's."""
+    data = orc.load_dataset(_raw(gold), compact_dataset=True)
+    a = Dataset(data, device=gpu)
+    b = Dataset(dict(data, actions=data['actions'] * -3.0 + 1.0), device=gpu)
+    s = _make_sampler(kind, a, seed=11)
+    x = s.sample(256, record_draws=True)
+    assert torch.equal(x['actions'], a['actions'][x['_idxs']])
+    s.dataset = b
+    y = s.sample(256, record_draws=True)
+    assert torch.equal(y['actions'], b['actions'][y['_idxs']])
+
+
+@pytest.mark.parametrize('row_record', [True, False])
+@pytest.mark.parametrize('kind', ['gc', 'hgc'])
+def test_replaced_unpacked_column(gpu, gold, kind, row_record):
+    """ds['observations'] = new (a column outside the row record) between a
+    call and its out= refill: the prepared batch holds the old tensor's
+    pointer, so the refill must not launch from it.  The sample's indices come
+    from a twin sampler (same seed, same call count)."""
+    data = orc.load_dataset(_raw(gold), compact_dataset=True)
+    ds = Dataset(data, device=gpu)
+    s = _make_sampler(kind, ds, seed=12, row_record=row_record)
+    twin = _make_sampler(kind, Dataset(data, device=gpu), seed=12, row_record=row_record)
+    prev = s.sample(256)
+    twin.sample(256)
+    old = ds['observations']  # stays alive: the stale pointer would read it, not freed memory
+    ds['observations'] = old + 1
+    cur = s.sample(256, out=prev)
+    idx = twin.sample(256, record_draws=True)['_idxs']
+    assert torch.equal(cur['observations'], ds['observations'][idx])
+    assert torch.equal(cur['next_observations'], ds['observations'][torch.clamp(idx + 1, max=ds.size - 1)])
+    assert torch.equal(cur['actions'], ds['actions'][idx])
+
+
+def _rand_draws_consumed(fn):
+    """How many np.random.rand() draws of numpy's global stream fn() consumes
+    (0..3), by comparing the stream's next draw against a RandomState replica."""
+    state = np.random.get_state()
+    try:
+        np.random.seed(123)
+        replica = np.random.RandomState(123).rand(4)
+        fn()
+        return list(replica).index(np.random.rand())
+    finally:
+        np.random.set_state(state)
+
+
+@pytest.mark.parametrize('kind', ['gc', 'hgc'])
+def test_p_aug_draws(gpu, gold, kind):
+    """One p_aug rule on every path: no draw of numpy's global stream with
+    p_aug 0 or under evaluation, exactly one per call with p_aug 0.5 (the
+    golden columns are 2-D, so no crop follows)."""
+    data = orc.load_dataset(_raw(gold), compact_dataset=True)
+    ds = Dataset(data, device=gpu)
+    for p_aug, want in ((0.0, 0), (0.5, 1)):
+        s = _make_sampler(kind, ds, seed=13, p_aug=p_aug)
+        assert _rand_draws_consumed(lambda: s.sample(64)) == want
+        batch = s.sample(64)
+        assert _rand_draws_consumed(lambda: s.sample(64, out=batch)) == want
+        assert _rand_draws_consumed(lambda: s.sample(64, record_draws=True)) == want
+        assert _rand_draws_consumed(lambda: s.sample(64, idxs=ds.valid_idxs[:64])) == want
+        assert _rand_draws_consumed(lambda: s.sample(64, evaluation=True)) == 0
+        assert _rand_draws_consumed(lambda: s.sample(64, out=batch, evaluation=True)) == 0
