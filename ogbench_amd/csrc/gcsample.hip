@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gc_select.h"
 
 namespace ogbx {
 
@@ -510,17 +511,7 @@ __global__ void __launch_bounds__(256) gc_ahead_kernel(
   }
 }
 
-// HGCDataset.compute_high_next_idxs (datasets.py:478-491) for one sample.
-__device__ inline void high_next(int64_t idx, int64_t fin, int64_t goal, int64_t K, int64_t* next,
-                                 int64_t* steps) {
-  int64_t st = K < fin - idx ? K : fin - idx;
-  const int64_t diff = goal - idx;
-  if (0 <= diff && diff < st) st = diff;
-  *steps = st;
-  *next = idx + st;
-}
-
-constexpr int kHgcSel = 10;
+// high_next (compute_high_next_idxs) and kHgcSel: gc_select.h
 
 // HGCDataset.sample (datasets.py:496-643): same tile structure as
 // gc_sample_kernel with ten row selectors and the hierarchical scalars.

@@ -15,6 +15,12 @@ trajectory-end lookup, hindsight goal relabel and the row gathers of every
 column are fused.  Random numbers come from a counter-based Philox stream
 (key = seed, counter = (sample, call)); the reference's NumPy draws can be
 injected bit-exactly through ``draws=`` for parity tests.
+
+Visual datasets (``frame_stack`` / ``p_aug``, as every ``visual-*`` line of
+the reference's hyperparameters.sh sets them): the image columns of a batch
+-- frame stacks and the random crop -- are written by one further launch,
+``visual_gather_kernel`` (``ogbx_visual_gather``, include/ogbx_visual.h), from
+the index outputs of the fused launch.  The frames stay unstacked in HBM.
 """
 
 from __future__ import annotations
@@ -131,6 +137,26 @@ class GcDrawRecord(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in _DRAW_ORDER]
 
 
+class VisualColumn(ctypes.Structure):
+    _fields_ = [
+        ('src', ctypes.c_void_p),
+        ('dst', ctypes.c_void_p),
+        ('height', ctypes.c_int32),
+        ('width', ctypes.c_int32),
+        ('px_bytes', ctypes.c_int32),
+        ('select', ctypes.c_int32),
+        ('stack', ctypes.c_int32),
+        ('crop', ctypes.c_int32),
+    ]
+
+
+class VisualIndices(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('idxs', 'value_goal_idxs', 'actor_goal_idxs', 'low_value_goal_idxs')]
+
+
+CROP_PADDING = 3  # GCDataset.augment (datasets.py:331)
+
+
 def _bind():
     L = _lib.lib()
     if not getattr(L, '_gc_bound', False):
@@ -166,6 +192,15 @@ def _bind():
         L.ogbx_nonzero_f32.restype = ctypes.c_int32
         L.ogbx_nonzero_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p]
+        # include/ogbx_visual.h (its own header and version; not part of ogbx.h)
+        L.ogbx_visual_api_version.restype = ctypes.c_int32
+        L.ogbx_visual_api_version.argtypes = []
+        L.ogbx_visual_gather.restype = ctypes.c_int32
+        L.ogbx_visual_gather.argtypes = [
+            P(GcBuffer), P(HgcConfig), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, P(VisualIndices),
+            ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64,
+            ctypes.c_void_p, ctypes.c_void_p,
+        ]
         L._gc_bound = True
     return L
 
@@ -309,7 +344,34 @@ class GCDataset:
     ``traj_end``, ``valid_idxs``) are fixed at construction, as the
     reference's ``__post_init__`` fixes its own: a new dataset must keep the
     trajectory layout.
+
+    Visual samplers.  With ``frame_stack = F`` the keys the reference builds
+    through get_observations / get_goal_observations (``observations``,
+    ``next_observations`` and, without ``oracle_reps``, ``value_goals`` /
+    ``actor_goals``) hold F frames stacked on the last axis: channel block j
+    is the frame at row max(r - (F-1-j), first row of r's trajectory)
+    (datasets.py:359-366).  ``next_observations`` selects min(idx + 1, R - 1);
+    the reference indexes idx + 1 unclamped and would raise on the last row,
+    which valid rows never reach.  ``frame_stack`` needs a compact dataset (no
+    'next_observations') and also stacks 2-D state observations
+    ([R, D] -> [B, F D]).  ``preprocess_frame_stack`` is accepted and has no
+    effect: the reference's two settings give identical batches, and here the
+    frames always stay unstacked in HBM (a third of the memory at F = 3), so
+    ``sampler.dataset['observations']`` stays unstacked too.  With
+    ``p_aug > 0`` and 4-D observations, a call whose coin comes up (one
+    ``np.random.rand()`` per call, not under ``evaluation``) crops those keys
+    with padding 3 and one offset pair per sample drawn on the device
+    (datasets.py:17-33, 329-339); this also works without ``frame_stack`` and
+    on a non-compact dataset.  A visual sampler runs the fused launch over its
+    other columns and one ``ogbx_visual_gather`` launch over the image ones;
+    it does not use the look-ahead plan.  Its non-image keys and indices are
+    those of the same sampler without ``frame_stack`` / ``p_aug`` at the same
+    seed and call.
     """
+
+    # the keys a visual sampler may stack, and of those the ones augment() crops
+    _VISUAL_KEYS = ('observations', 'next_observations', 'value_goals', 'actor_goals')
+    _CROP_KEYS = _VISUAL_KEYS
 
     def __init__(self, dataset, config, preprocess_frame_stack=True, seed=None, _plain=False):
         torch = _torch()
@@ -320,8 +382,12 @@ class GCDataset:
         self.preprocess_frame_stack = preprocess_frame_stack
         self.size = dataset.size
         self.device = dataset.device
-        if config.get('frame_stack') is not None:
-            raise NotImplementedError('frame stacking (visual datasets) is out of scope')
+        fs = config.get('frame_stack')
+        self._frame_stack = int(fs) if fs is not None else None
+        if fs is not None:
+            # only compact (observation-only) datasets (datasets.py:206-208)
+            assert 'next_observations' not in dataset
+            assert 1 <= self._frame_stack <= 8 and dataset['observations'].dim() >= 2
         if config.get('agent_name') in ('trl', 'latent_trl', 'discrete_latent_trl'):
             raise NotImplementedError('the TRL sampling branches are out of scope')
         L = _bind()
@@ -388,6 +454,10 @@ class GCDataset:
         # follow), so it is skipped here.
         self._p_aug = config.get('p_aug')
         self._p_aug_live = self._p_aug is not None and float(self._p_aug) > 0.0
+        # visual: some column is stacked or may be cropped (4-D observations)
+        self._visual = not _plain and (fs is not None or (self._p_aug_live and any(
+            dataset[k].dim() == 4 for k in ('observations', 'next_observations') if k in dataset)))
+        self._vis_cache = {}
         self._dev_idx = self.device.index
         self._plan_sample = L.ogbx_gc_plan_sample
         self._raw_stream = torch._C._cuda_getCurrentRawStream  # hipStream_t of the current stream, as an int
@@ -493,13 +563,42 @@ class GCDataset:
         self._calls += 1
         return self._seed, call
 
-    def _columns(self, total, keys):
-        """Column descriptors and the output dict (reference key order)."""
+    def _visual_spec(self, src_key, dst_key):
+        """(stack, crop) when ``dst_key`` is an image column of this visual
+        sampler (written by ogbx_visual_gather), else None (a fused column)."""
+        if not self._visual or dst_key not in self._VISUAL_KEYS:
+            return None
+        if src_key not in ('observations', 'next_observations'):
+            return None  # oracle_reps: neither stacked nor cropped
+        stack = self._frame_stack is not None
+        crop = self._p_aug_live and self.dataset[src_key].dim() == 4 and dst_key in self._CROP_KEYS
+        return (stack, crop) if (stack or crop) else None
+
+    def _vcolumn(self, src_key, select, spec, total):
+        """Destination tensor and descriptor of one image column."""
+        src = self.dataset[src_key]
+        stack, crop = spec
+        shape = tuple(src.shape[1:])
+        F = self._frame_stack if stack else 1
+        dst = _torch().empty((total,) + shape[:-1] + (shape[-1] * F,), dtype=src.dtype, device=self.device)
+        # an image is [H, W, C]; any other row is a 1-row image of its leading elements
+        H, W = (shape[0], shape[1]) if len(shape) == 3 else (1, int(np.prod(shape[:-1], dtype=np.int64)))
+        return dst, VisualColumn(src.data_ptr(), dst.data_ptr(), H, W, shape[-1] * src.element_size(), select,
+                                 int(stack), int(crop))
+
+    def _columns(self, total, keys, vcols=None):
+        """Column descriptors and the output dict (reference key order); the
+        image columns of a visual sampler go to ``vcols``."""
         torch = _torch()
         ds = self.dataset
         out, cols = {}, []
 
         def add(src_key, dst_key, select):
+            spec = self._visual_spec(src_key, dst_key) if vcols is not None else None
+            if spec is not None:
+                out[dst_key], vc = self._vcolumn(src_key, select, spec, total)
+                vcols.append(vc)
+                return
             src = ds[src_key]
             dst = torch.empty((total,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
             out[dst_key] = dst
@@ -558,12 +657,12 @@ class GCDataset:
     _what = 'gc_sample'  # names the call in error messages
     _draw_keys = _DRAW_ORDER  # the draws a recording call reports
 
-    def _batch(self, total, keys, record):
+    def _batch(self, total, keys, record, vcols=None):
         """A new batch: the output dict, the column descriptors, the scalar
         outputs as ``_set_batch`` / ``_direct`` pass them on, tensors to keep
         alive with the batch, and the index keys of a recording call."""
         torch = _torch()
-        out, cols = self._columns(total, keys)
+        out, cols = self._columns(total, keys, vcols)
         masks = torch.empty(total, dtype=torch.float64, device=self.device)
         rewards = torch.empty(total, dtype=torch.float64, device=self.device)
         # index outputs only when asked for (plain sampling or draw recording)
@@ -600,8 +699,11 @@ class GCDataset:
 
         draws: optional dict of injected reference draws (see ``_DRAW_ORDER``,
         for HGCDataset also the low-level ``l_*`` draws; device or host arrays
-        of length num_batches*batch_size).
-        record_draws: also return the draws the kernel used (``out['_draws']``).
+        of length num_batches*batch_size).  A visual sampler also takes
+        ``'crop_from'``, the [num_batches*batch_size, 2] offsets (cy, cx) of
+        augment()'s randint (datasets.py:333), used when the call crops.
+        record_draws: also return the draws the kernel used (``out['_draws']``;
+        with ``'crop_from'`` on a call that cropped, and without it otherwise).
         num_batches > 1: sample that many independent batches in the same launch
         (outputs have a leading num_batches*batch_size dimension).
         out: a batch dict returned by an earlier call with the same batch_size /
@@ -609,6 +711,8 @@ class GCDataset:
         in place (stream ordered, so consumers enqueued earlier read the old
         batch) and it is returned.  Skips all per-call allocation.
         """
+        if self._visual:
+            return self._sample_visual(int(batch_size), int(num_batches), idxs, evaluation, draws, record_draws, out)
         plain_call = idxs is None and not draws and not record_draws and _keys is None
         # the staleness token: the dataset object, its generation (no column
         # replaced) and the packed columns' version counters (none modified in
@@ -632,23 +736,18 @@ class GCDataset:
             out, extra = self._sample_new(int(batch_size), int(num_batches), idxs, draws, record_draws, _keys,
                                           plain_call, (batch_size, num_batches))
         if self._p_aug_live and not evaluation:
-            # image crops apply only to 4-D arrays (datasets.py:278-279)
-            if np.random.rand() < self._p_aug and any(v.dim() == 4 for v in out.values()):
-                raise NotImplementedError('image augmentation (visual datasets) is out of scope')
+            # the coin of datasets.py:278-279; crops apply only to 4-D arrays,
+            # and a sampler with 4-D observations is visual (_sample_visual)
+            np.random.rand()
         if extra:
             out.update(extra)
         return out
 
-    def _sample_new(self, B, nb, idxs, draws, record_draws, keys, plain_call, shape):
-        """A call into a new batch: allocate it, stage idxs / draws, launch
-        through the plan (plain call; the batch's slot is remembered for
-        ``out=``) or the direct entry point.  Returns the batch and the ``_*``
-        keys a recording call adds to it."""
+    def _stage(self, total, idxs, draws, record_draws):
+        """Explicit idxs and injected draws on the device, and the record
+        buffers of a recording call: (draws struct, tensors to keep alive until
+        the launch was issued, record struct or None, its tensors or None)."""
         torch = _torch()
-        total = B * nb
-        out, cols, scalars, keep, idx_t = self._batch(total, keys, record_draws)
-        col_keep = (GcColumn * max(1, len(cols)))(*cols)
-        col_arr = ctypes.cast(col_keep, ctypes.c_void_p)
         staged = []
         dr, gdr = self._draw_structs()
         if idxs is not None:
@@ -668,6 +767,78 @@ class GCDataset:
             rec_t = {k: torch.empty(total, dtype=torch.int64 if k in _HDRAW_INT else torch.float64,
                                     device=self.device) for k in self._draw_keys}
             rec = self._record_struct(rec_t)
+        return dr, staged, rec, rec_t
+
+    # ------------------------------------------------------------ visual batches
+    def _visual_indices(self, idx_t):
+        """The fused launch's index outputs as ogbx_visual_gather reads them."""
+        return VisualIndices(idx_t['_idxs'].data_ptr(), idx_t['_value_goal_idxs'].data_ptr(),
+                             idx_t['_actor_goal_idxs'].data_ptr(), None)
+
+    def _sample_visual(self, B, nb, idxs, evaluation, draws, record_draws, out):
+        """sample() of a visual sampler: the fused direct launch over the
+        non-image columns with the index outputs requested, then one
+        ogbx_visual_gather launch over the image columns."""
+        torch = _torch()
+        total = B * nb
+        ds = self.dataset
+        if (ds is not self._tok_ds or getattr(ds, '_gen', None) != self._tok_gen
+                or (self._rec_src and tuple(map(_VERSION, self._rec_tensors)) != self._rec_versions)):
+            self._refresh_record()
+            self._vis_cache.clear()
+        # the coin stays on the host (datasets.py:278-279); the offsets are device draws
+        crop = bool(self._p_aug_live and not evaluation and np.random.rand() < self._p_aug)
+        draws = dict(draws or {})
+        crop_from = draws.pop('crop_from', None)
+        cf = None
+        if crop and crop_from is not None:
+            cf = _to_device(crop_from, self.device).to(torch.int64)
+            if tuple(cf.shape) != (total, 2):
+                raise ValueError(f"draws['crop_from'] must have shape ({total}, 2), got {tuple(cf.shape)}")
+        # as in the fused path, only a call without idxs / draws / recording
+        # prepares a batch that ``out=`` can refill
+        plain_call = idxs is None and not draws and crop_from is None and not record_draws
+        hit = self._vis_cache.get(id(out)) if (out is not None and plain_call) else None
+        if hit is not None and hit[0] is out and hit[1] == (B, nb):
+            st = hit[2]
+        else:
+            vcols = []
+            out, cols, scalars, keep, idx_t = self._batch(total, None, True, vcols)
+            col_keep = (GcColumn * max(1, len(cols)))(*cols)
+            vcol_keep = (VisualColumn * max(1, len(vcols)))(*vcols)
+            st = (ctypes.cast(col_keep, ctypes.c_void_p), len(cols), scalars, ctypes.cast(vcol_keep, ctypes.c_void_p),
+                  len(vcols), self._visual_indices(idx_t), idx_t, (col_keep, vcol_keep, keep))
+            if plain_call:
+                if len(self._vis_cache) >= 2:
+                    self._vis_cache.clear()
+                self._vis_cache[id(out)] = (out, (B, nb), st)
+        col_arr, ncols, scalars, vcol_arr, nvcols, vidx, idx_t, _ = st
+        dr, staged, rec, rec_t = self._stage(total, idxs, draws, record_draws)
+        cf_out = torch.empty((total, 2), dtype=torch.int64, device=self.device) if (crop and record_draws) else None
+        seed, call = self._next_seed()
+        stream = _lib.stream_of(self.device)
+        _lib.check(self._direct(col_arr, ncols, B, nb, dr, seed, call, scalars, rec, stream), self._what)
+        _lib.check(self._L.ogbx_visual_gather(
+            self._buf, self._hcfg_ptr(), vcol_arr, nvcols, total, vidx, self._frame_stack or 1, CROP_PADDING,
+            _lib.ptr(cf), int(crop and cf is None), seed, call, _lib.ptr(cf_out), stream), 'visual_gather')
+        del staged, cf  # alive until the launches were issued
+        if record_draws:
+            if cf_out is not None:
+                rec_t['crop_from'] = cf_out
+            out.update({'_draws': rec_t, **idx_t})
+        return out
+
+    def _sample_new(self, B, nb, idxs, draws, record_draws, keys, plain_call, shape):
+        """A call into a new batch: allocate it, stage idxs / draws, launch
+        through the plan (plain call; the batch's slot is remembered for
+        ``out=``) or the direct entry point.  Returns the batch and the ``_*``
+        keys a recording call adds to it."""
+        torch = _torch()
+        total = B * nb
+        out, cols, scalars, keep, idx_t = self._batch(total, keys, record_draws)
+        col_keep = (GcColumn * max(1, len(cols)))(*cols)
+        col_arr = ctypes.cast(col_keep, ctypes.c_void_p)
+        dr, staged, rec, rec_t = self._stage(total, idxs, draws, record_draws)
         seed, call = self._next_seed()
         stream = _lib.stream_of(self.device)
         if plain_call:
@@ -764,7 +935,20 @@ class HGCDataset(GCDataset):
     high_subgoal_steps, value_subgoal_steps, actor_subgoal_steps,
     low_subgoal_steps, low_discount.  One fused launch of hgc_sample_kernel
     per sample() returns the reference's 27 (28 with low_discount) keys.
+
+    As a visual sampler (see GCDataset) it stacks every key the reference
+    builds through get_observations / get_goal_observations / get_high_actions
+    (the goal-type ones only without ``oracle_reps``) and crops exactly the
+    keys of the reference's augment list (datasets.py:625-640):
+    ``high_value_reps`` (bound to the observations before augment rebinds
+    them) and ``low_value_goals`` (not in the list) stay uncropped.
     """
+
+    _VISUAL_KEYS = ('observations', 'next_observations', 'high_value_reps', 'high_value_goals', 'high_value_actions',
+                    'high_value_next_observations', 'low_value_next_observations', 'low_value_goals',
+                    'high_actor_goals', 'high_actor_actions', 'high_actor_next_observations', 'low_actor_goals',
+                    'low_actor_goal_observations', 'low_actor_next_observations')
+    _CROP_KEYS = tuple(k for k in _VISUAL_KEYS if k not in ('high_value_reps', 'low_value_goals'))
 
     def _hcfg_ptr(self):
         return ctypes.byref(self._hcfg)
@@ -789,14 +973,20 @@ class HGCDataset(GCDataset):
         )
         self._Lh = _bind_hgc()
 
-    def _hcolumns(self, total):
-        """Output tensors in the reference's key order, and column descriptors."""
+    def _hcolumns(self, total, vcols=None):
+        """Output tensors in the reference's key order, and column descriptors
+        (the image columns of a visual sampler go to ``vcols``)."""
         torch = _torch()
         ds = self.dataset
         out, cols = {}, []
         goal_src = 'oracle_reps' if 'oracle_reps' in ds else 'observations'
 
-        def col(src_key, select):
+        def col(src_key, select, key=None):
+            spec = self._visual_spec(src_key, key) if vcols is not None else None
+            if spec is not None:
+                dst, vc = self._vcolumn(src_key, select, spec, total)
+                vcols.append(vc)
+                return dst
             src = ds[src_key]
             dst = torch.empty((total,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
             cols.append(self._column(src_key, dst, select))
@@ -806,41 +996,46 @@ class HGCDataset(GCDataset):
             return torch.empty(total, dtype=dtype, device=self.device)
 
         for k in ds.keys():
-            out[k] = col(k, 0)
+            out[k] = col(k, 0, k)
         if 'next_observations' not in ds:
-            out['next_observations'] = col('observations', 1)
+            out['next_observations'] = col('observations', 1, 'next_observations')
         i64, f64 = torch.int64, torch.float64
-        out['high_value_reps'] = out['observations']
-        out['high_value_goals'] = col(goal_src, 2)
-        out['high_value_actions'] = col(goal_src, 4)
-        out['high_value_next_observations'] = col('observations', 4)
+        # a visual batch's observations may be cropped; high_value_reps never is
+        out['high_value_reps'] = col('observations', 0, 'high_value_reps') if vcols is not None \
+            else out['observations']
+        out['high_value_goals'] = col(goal_src, 2, 'high_value_goals')
+        out['high_value_actions'] = col(goal_src, 4, 'high_value_actions')
+        out['high_value_next_observations'] = col('observations', 4, 'high_value_next_observations')
         for k, dt in (('high_value_offsets', i64), ('high_value_subgoal_steps', i64), ('high_value_masks', f64),
                       ('high_value_rewards', f64)):
             out[k] = scalar(dt)
-        out['low_value_next_observations'] = col('observations', 5)
+        out['low_value_next_observations'] = col('observations', 5, 'low_value_next_observations')
         for k, dt in (('low_value_subgoal_steps', i64), ('low_value_masks', f64), ('low_value_rewards', f64)):
             out[k] = scalar(dt)
         if self._has_low:
-            out['low_value_goals'] = col(goal_src, 6)
+            out['low_value_goals'] = col(goal_src, 6, 'low_value_goals')
         out['value_goals'] = out['high_value_goals']
         out['masks'] = scalar(f64)
         out['rewards'] = scalar(f64)
-        out['high_actor_goals'] = col(goal_src, 3)
-        out['high_actor_actions'] = col(goal_src, 7)
-        out['high_actor_next_observations'] = col('observations', 7)
+        out['high_actor_goals'] = col(goal_src, 3, 'high_actor_goals')
+        out['high_actor_actions'] = col(goal_src, 7, 'high_actor_actions')
+        out['high_actor_next_observations'] = col('observations', 7, 'high_actor_next_observations')
         out['high_actor_targets'] = out['high_actor_actions']
-        out['low_actor_goals'] = col(goal_src, 8)
-        out['low_actor_goal_observations'] = col('observations', 8)
-        out['low_actor_next_observations'] = col('observations', 9)
+        out['low_actor_goals'] = col(goal_src, 8, 'low_actor_goals')
+        out['low_actor_goal_observations'] = col('observations', 8, 'low_actor_goal_observations')
+        out['low_actor_next_observations'] = col('observations', 9, 'low_actor_next_observations')
         return out, cols
 
     # sample() is GCDataset's; what differs for the hierarchical sampler:
     _what = 'hgc_sample'
 
-    def _batch(self, total, keys, record):
+    def _visual_indices(self, idx_t):
+        return VisualIndices(*[idx_t['_' + k].data_ptr() for k in _HGC_SCALARS[:4]])
+
+    def _batch(self, total, keys, record, vcols=None):
         torch = _torch()
         assert keys is None
-        out, cols = self._hcolumns(total)
+        out, cols = self._hcolumns(total, vcols)
         idx_t = {k: torch.empty(total, dtype=torch.int64, device=self.device)
                  for k in (_HGC_SCALARS[:4] if record else ())}
         outs = HgcOutputs(*[_lib.ptr(idx_t.get(k)) for k in _HGC_SCALARS[:4]],
