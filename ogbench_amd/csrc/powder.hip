@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "common.h"
+#include "powder_schedule.h"
 
 namespace ogbx {
 
@@ -103,30 +104,6 @@ struct PowderState {
   // B), so a render-only step reads 3 bytes per cell instead of id + velocity
   uint16_t* crg;     // [N, H*W]
   uint8_t* cb;       // [N, H*W]
-};
-
-// Next-episode reset states prepared ahead (medium / hard, ogbx_powder_step):
-// an auto-reset's goal replay and initial state depend only on the env's
-// task, its next episode number and the seed (Philox), not on the episode
-// being played, so pwf_prepare_kernel computes them on a low-priority side
-// stream during the episode, a few replay ops per launch, into these shadow
-// buffers.  The synchronized auto-reset step then loads them instead of
-// replaying.  tag / ep / q: the host epoch the shadow belongs to (bumped by
-// every reset or seed change), the episode and task it is for, and the next
-// replay op (q > len: complete).  use != 0 only on a step the host
-// joined the side stream before; any mismatch replays in line, so results
-// never depend on the schedule.
-struct PwPrep {
-  uint8_t* world;
-  int8_t* mom;
-  float2* vel;
-  uint8_t* goal;
-  uint32_t* tag;
-  uint32_t* ep;
-  int32_t* q;
-  int32_t* task;
-  uint32_t epoch;
-  int32_t use;
 };
 
 template <int WS>
@@ -677,54 +654,6 @@ __global__ void __launch_bounds__(pwf_nt<WS>()) __attribute__((amdgpu_waves_per_
   }
 }
 
-// Up to `ops` replay ops of every env's next-episode reset (PwPrep), from
-// its shadow (or the blank world at op 0): the same pwf_reset_op sequence,
-// Philox slots and draws as an in-line auto-reset of episode S.episode + 1.
-// S.episode / S.ctrl are read while the main stream may be stepping (a
-// stale episode gives a shadow for an episode that never comes: not used).
-template <int WS>
-__global__ void __launch_bounds__(pwf_nt<WS>()) __attribute__((amdgpu_waves_per_eu(kPwfWaves))) pwf_prepare_kernel(
-    const PowderParams* __restrict__ Pp, PowderState S, PwPrep prep, int32_t ops, uint32_t k0, uint32_t k1,
-    uint32_t r0, uint32_t r1) {
-  constexpr int C = WS * WS;
-  __shared__ PwFullShared<WS> sh;
-  const int64_t e = blockIdx.x;
-  const uint64_t ge = (uint64_t)e + (uint64_t)Pp->env_base;
-  const uint32_t target = __builtin_amdgcn_readfirstlane(S.episode[e]) + 1u;
-  int task = (__builtin_amdgcn_readfirstlane(S.ctrl[e]) >> 16) & 255;
-  if (task < 1 || task > Pp->num_tasks) task = 1;
-  const int len = Pp->seq_len[task - 1];
-  int q = (prep.tag[e] == prep.epoch && prep.ep[e] == target && prep.task[e] == task) ? prep.q[e] : 0;
-  q = __builtin_amdgcn_readfirstlane(q);
-  if (q > len) return;  // complete (uniform over the workgroup)
-  FW<WS> fw(sh);
-#ifdef OGBX_PWF_RULE_STAMPS
-  fw.diag_env = e;
-#endif
-  pwf_tables(sh, Pp);
-  if (q > 0) {
-    fw.load(prep.world + (size_t)e * C, prep.mom + (size_t)e * C, prep.vel + (size_t)e * C);
-    __syncthreads();
-  }
-  const int ne = Pp->num_elems, xy = Pp->xy_size;
-  const int re = (int)pw_draw(ge, target, 1, k0, k1, (uint32_t)ne);
-  const int rx = (int)pw_draw(ge, target, 2, k0, k1, (uint32_t)xy);
-  const int ry = (int)pw_draw(ge, target, 3, k0, k1, (uint32_t)xy);
-  for (int j = 0; j < ops && q <= len; ++j, ++q)
-    pwf_reset_op(fw, Pp, task, q, re, rx, ry, nullptr, r0, r1, ge, target, nullptr);
-  if (q > len) {
-#pragma unroll
-    for (int k = 0; k < FW<WS>::CPT; ++k) prep.goal[(size_t)e * C + fw.cell(k)] = sh.g[fw.cell(k)];
-  }
-  fw.store(prep.world + (size_t)e * C, prep.mom + (size_t)e * C, prep.vel + (size_t)e * C);
-  if (threadIdx.x == 0) {
-    prep.q[e] = q;
-    prep.ep[e] = target;
-    prep.task[e] = task;
-    prep.tag[e] = prep.epoch;
-  }
-}
-
 // k_steps env steps; rand: [k, N, 3, H, W] injected fields for the forward of
 // each third step, or NULL = Philox (auto-resets always use Philox).
 
@@ -740,7 +669,7 @@ __global__ void __launch_bounds__(pwf_nt<WS>()) __attribute__((amdgpu_waves_per_
     float* __restrict__ reward, uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated,
     uint8_t* __restrict__ success, int32_t auto_reset, uint32_t k0, uint32_t k1, uint32_t a0, uint32_t a1,
     uint32_t r0, uint32_t r1, const uint8_t* __restrict__ skip, int32_t refresh, int32_t chunk,
-    const int32_t* __restrict__ order, uint32_t* __restrict__ cost, PwPrep prep) {
+    const int32_t* __restrict__ order, uint32_t* __restrict__ cost) {
   constexpr int C = WS * WS, CPT = FW<WS>::CPT;
   __shared__ PwFullShared<WS> sh;
   FW<WS> fw(sh);
@@ -812,7 +741,7 @@ __global__ void __launch_bounds__(pwf_nt<WS>()) __attribute__((amdgpu_waves_per_
     // one inlined forward)
     int op = fw_step ? -1 : 0, op_end = fw_step ? -1 : -2;
     int re = 0, rx = 0, ry = 0;
-    bool reset = false, shadow = false;
+    bool reset = false;
     auto finish_step = [&]() {
       if (threadIdx.x == 0) {
         reward[o] = succ ? 1.0f : 0.0f;
@@ -823,16 +752,10 @@ __global__ void __launch_bounds__(pwf_nt<WS>()) __attribute__((amdgpu_waves_per_
       if (auto_reset && (succ || trunc)) {
         reset = true;
         ep += 1u;
-        // the episode's reset state prepared ahead (PwPrep), else in line
-        shadow = prep.use && prep.tag[e] == prep.epoch && prep.ep[e] == ep && prep.task[e] == task &&
-                 prep.q[e] > len;
-        shadow = __builtin_amdgcn_readfirstlane((int)shadow) != 0;
-        if (!shadow) {
-          re = (int)pw_draw(ge, ep, 1, k0, k1, (uint32_t)ne);
-          rx = (int)pw_draw(ge, ep, 2, k0, k1, (uint32_t)xy);
-          ry = (int)pw_draw(ge, ep, 3, k0, k1, (uint32_t)xy);
-          op_end = len;
-        }
+        re = (int)pw_draw(ge, ep, 1, k0, k1, (uint32_t)ne);
+        rx = (int)pw_draw(ge, ep, 2, k0, k1, (uint32_t)xy);
+        ry = (int)pw_draw(ge, ep, 3, k0, k1, (uint32_t)xy);
+        op_end = len;
       }
     };
     if (!fw_step) finish_step();
@@ -847,13 +770,6 @@ __global__ void __launch_bounds__(pwf_nt<WS>()) __attribute__((amdgpu_waves_per_
       } else {
         pwf_reset_op(fw, Pp, task, op, re, rx, ry, nullptr, r0, r1, ge, ep, nullptr);
       }
-    }
-    if (shadow) {
-      __syncthreads();  // every lane is past its last read of the stepped world
-      fw.load(prep.world + (size_t)e * C, prep.mom + (size_t)e * C, prep.vel + (size_t)e * C);
-#pragma unroll
-      for (int kk = 0; kk < CPT; ++kk) sh.g[fw.cell(kk)] = prep.goal[(size_t)e * C + fw.cell(kk)];
-      __syncthreads();
     }
     if (reset) {
       succ = fw.errors() < tol;
@@ -1300,36 +1216,15 @@ struct ogbx_powder_env {
   uint8_t* handled = nullptr;  // medium/hard: [N] env stepped by pwf_light_step_kernel this launch
   uint32_t* cost = nullptr;    // medium/hard: [N] shader cycles of the env's last one-env full-kernel workgroup
   int32_t* order = nullptr;    // medium/hard: [N] workgroup -> env of an in-phase full step, costliest first
-  // the last light launch sorted `order` for the step after it (by task
-  // length if order_by_task); consumed by that step when it is the in-phase
-  // full step the host expected.  A stale order is still a permutation of the
-  // envs: only the schedule would differ.
-  bool order_ready = false, order_by_task = false;
+  PwfSchedule sched;           // medium/hard: what the host knows of the coming steps (powder_schedule.h)
   bool light = true;           // split render-only steps into pwf_light_step_kernel
   // the render cache (S.crg / S.cb) may disagree with the state: set at create
   // and whenever a world or velocity pointer is handed out (the caller may
   // write through it); the next step then renders from the state and rewrites
   // the cache of every env
   bool cache_stale = true;
-  // steps since the last reset of every env (-1: unknown, e.g. after a masked
-  // reset).  Envs reset together step in phase, so the host can tell the
-  // steps on which every in-phase env needs the full kernel (its forward
-  // step, or the synchronized truncation + auto-reset) and not launch
-  // pwf_light_step_kernel, whose every workgroup would exit.  A wrong guess
-  // is harmless: pwf_step_kernel without the skip list steps render-only
-  // envs itself, bit-identically (only slower), so out-of-phase envs (an
-  // earlier success + auto-reset, a restored state) stay correct.
-  int64_t phase = -1;
   uint64_t seed = 0;
   bool was_reset = false;
-  // next-episode reset states prepared ahead on a low-priority side stream
-  // (PwPrep; medium / hard, in-phase envs with auto-reset)
-  int32_t prep_ops = 0;           // replay ops per prepare launch (0: off, the default; OGBX_PWF_PREP_OPS)
-  ogbx::PwPrep prep{};            // device buffers + the current epoch
-  hipStream_t side = nullptr;     // created on first use, lowest priority
-  hipEvent_t ev_fork = nullptr, ev_side = nullptr;
-  int64_t prep_launched = 0;      // replay ops launched for the coming synchronized reset
-  bool side_pending = false;      // a prepare launch not yet joined
 };
 
 using namespace ogbx;
@@ -1340,29 +1235,16 @@ template <int WS>
 constexpr auto pwf_step_kernel_dense = pwf_step_kernel<WS, false>;
 template <int WS>
 constexpr auto pwf_step_kernel_sparse = pwf_step_kernel<WS, true>;
-#define PWF_LAUNCH(kern, e, grid, stream, ...)                                                 \
-  do {                                                                                         \
-    if ((e)->P.W == 64)                                                                        \
-      hipLaunchKernelGGL(kern<64>, dim3(grid), dim3(pwf_nt<64>()), 0, (hipStream_t)(stream), __VA_ARGS__); \
-    else                                                                                       \
-      hipLaunchKernelGGL(kern<32>, dim3(grid), dim3(pwf_nt<32>()), 0, (hipStream_t)(stream), __VA_ARGS__); \
+// nt: the block size as a template of the world size (pw_nt / pwf_nt)
+#define PW_LAUNCH(kern, nt, e, grid, stream, ...)                                                     \
+  do {                                                                                                \
+    if ((e)->P.W == 64)                                                                               \
+      hipLaunchKernelGGL(kern<64>, dim3(grid), dim3(nt<64>()), 0, (hipStream_t)(stream), __VA_ARGS__); \
+    else                                                                                              \
+      hipLaunchKernelGGL(kern<32>, dim3(grid), dim3(nt<32>()), 0, (hipStream_t)(stream), __VA_ARGS__); \
   } while (0)
-// Every prepared reset state so far is void (a reset or a new seed: the
-// Philox keys change): new epoch; in-flight prepare launches finish under the
-// old one, whose shadows are never used.  A caller's writes through the state
-// pointers need no epoch: a shadow is used only for the episode number and
-// task the env holds at its reset.
-inline void prep_invalidate(ogbx_powder_env* e) {
-  e->prep.epoch += 1u;
-  e->prep_launched = 0;
-}
-#define PW_LAUNCH(kern, e, grid, stream, ...)                                                  \
-  do {                                                                                         \
-    if ((e)->P.W == 64)                                                                        \
-      hipLaunchKernelGGL(kern<64>, dim3(grid), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__); \
-    else                                                                                       \
-      hipLaunchKernelGGL(kern<32>, dim3(grid), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__); \
-  } while (0)
+template <int WS>
+constexpr int pw_nt() { return 256; }  // easy worlds and the light kernel
 }  // namespace
 
 extern "C" {
@@ -1451,52 +1333,32 @@ ogbx_status ogbx_powder_create(const ogbx_powder_opts* opts, int64_t n_envs, int
       for (int k = 0; k < 3; ++k) P.seq[t][q][k] = (int8_t)tasks[t][q][k];
   }
   const size_t n = (size_t)n_envs, HW = (size_t)ws * ws;
-  hipError_t h = hipMalloc(&e->Pd, sizeof(PowderParams));
+  hipError_t h = hipSuccess;
+  // allocate (zero: and clear) unless an earlier call failed
+  auto alloc = [&h](auto** p, size_t bytes, bool zero = false) {
+    if (h == hipSuccess) h = hipMalloc(p, bytes);
+    if (h == hipSuccess && zero) h = hipMemset(*p, 0, bytes);
+  };
+  alloc(&e->Pd, sizeof(PowderParams));
   if (h == hipSuccess) h = hipMemcpy(e->Pd, &P, sizeof(PowderParams), hipMemcpyHostToDevice);
-  if (h == hipSuccess) h = hipMalloc(&e->S.world, n * HW);
-  if (h == hipSuccess) h = hipMalloc(&e->S.ctrl, n * sizeof(int32_t));
-  if (h == hipSuccess) h = hipMalloc(&e->S.elapsed, n * sizeof(int32_t));
-  if (h == hipSuccess) h = hipMalloc(&e->S.episode, n * sizeof(uint32_t));
-  if (h == hipSuccess) h = hipMemset(e->S.world, 0, n * HW);
-  if (h == hipSuccess) h = hipMemset(e->S.ctrl, 0, n * sizeof(int32_t));
-  if (h == hipSuccess) h = hipMemset(e->S.elapsed, 0, n * sizeof(int32_t));
-  if (h == hipSuccess) h = hipMemset(e->S.episode, 0, n * sizeof(uint32_t));
+  alloc(&e->S.world, n * HW, true);
+  alloc(&e->S.ctrl, n * sizeof(int32_t), true);
+  alloc(&e->S.elapsed, n * sizeof(int32_t), true);
+  alloc(&e->S.episode, n * sizeof(uint32_t), true);
   if (e->full) {
-    if (h == hipSuccess) h = hipMalloc(&e->S.mom, n * HW);
-    if (h == hipSuccess) h = hipMalloc(&e->S.vel, n * HW * sizeof(float2));
-    if (h == hipSuccess) h = hipMalloc(&e->S.goal_env, n * HW);
-    if (h == hipSuccess) h = hipMalloc(&e->S.crg, n * HW * sizeof(uint16_t));
-    if (h == hipSuccess) h = hipMalloc(&e->S.cb, n * HW);
-    if (h == hipSuccess) h = hipMalloc(&e->handled, n);
-    if (h == hipSuccess) h = hipMalloc(&e->cost, n * sizeof(uint32_t));
-    if (h == hipSuccess) h = hipMalloc(&e->order, n * sizeof(int32_t));
-    if (h == hipSuccess) h = hipMemset(e->cost, 0, n * sizeof(uint32_t));
+    alloc(&e->S.mom, n * HW, true);
+    alloc(&e->S.vel, n * HW * sizeof(float2), true);
+    alloc(&e->S.goal_env, n * HW, true);
+    alloc(&e->S.crg, n * HW * sizeof(uint16_t));
+    alloc(&e->S.cb, n * HW);
+    alloc(&e->handled, n);
+    alloc(&e->cost, n * sizeof(uint32_t), true);
+    alloc(&e->order, n * sizeof(int32_t));
     if (const char* v = std::getenv("OGBX_PWF_LIGHT")) e->light = std::atoi(v) != 0;  // A/B knob
-    if (const char* v = std::getenv("OGBX_PWF_PREP_OPS")) e->prep_ops = std::max(0, std::atoi(v));  // A/B knob
-    if (e->prep_ops > 0) {
-      if (h == hipSuccess) h = hipMalloc(&e->prep.world, n * HW);
-      if (h == hipSuccess) h = hipMalloc(&e->prep.mom, n * HW);
-      if (h == hipSuccess) h = hipMalloc(&e->prep.vel, n * HW * sizeof(float2));
-      if (h == hipSuccess) h = hipMalloc(&e->prep.goal, n * HW);
-      if (h == hipSuccess) h = hipMalloc(&e->prep.tag, n * sizeof(uint32_t));
-      if (h == hipSuccess) h = hipMalloc(&e->prep.ep, n * sizeof(uint32_t));
-      if (h == hipSuccess) h = hipMalloc(&e->prep.q, n * sizeof(int32_t));
-      if (h == hipSuccess) h = hipMalloc(&e->prep.task, n * sizeof(int32_t));
-      if (h == hipSuccess) h = hipMemset(e->prep.tag, 0, n * sizeof(uint32_t));
-      e->prep.epoch = 1;  // tag 0: never prepared
-      int least = 0, greatest = 0;
-      if (h == hipSuccess) h = hipDeviceGetStreamPriorityRange(&least, &greatest);
-      if (h == hipSuccess) h = hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, least);
-      if (h == hipSuccess) h = hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming);
-      if (h == hipSuccess) h = hipEventCreateWithFlags(&e->ev_side, hipEventDisableTiming);
-    }
-    if (h == hipSuccess) h = hipMemset(e->S.mom, 0, n * HW);
-    if (h == hipSuccess) h = hipMemset(e->S.vel, 0, n * HW * sizeof(float2));
-    if (h == hipSuccess) h = hipMemset(e->S.goal_env, 0, n * HW);
   } else {
-    if (h == hipSuccess) h = hipMalloc(&e->goals, (size_t)P.num_tasks * HW);
+    alloc(&e->goals, (size_t)P.num_tasks * HW);
     if (h == hipSuccess) {
-      PW_LAUNCH(pw_goal_kernel, e, P.num_tasks, 0, e->Pd, e->goals);
+      PW_LAUNCH(pw_goal_kernel, pw_nt, e, P.num_tasks, 0, e->Pd, e->goals);
       h = hipGetLastError();
     }
   }
@@ -1526,18 +1388,6 @@ ogbx_status ogbx_powder_destroy(ogbx_powder_t e) {
   (void)hipFree(e->handled);
   (void)hipFree(e->cost);
   (void)hipFree(e->order);
-  if (e->side) (void)hipStreamSynchronize(e->side);
-  (void)hipFree(e->prep.world);
-  (void)hipFree(e->prep.mom);
-  (void)hipFree(e->prep.vel);
-  (void)hipFree(e->prep.goal);
-  (void)hipFree(e->prep.tag);
-  (void)hipFree(e->prep.ep);
-  (void)hipFree(e->prep.q);
-  (void)hipFree(e->prep.task);
-  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  if (e->ev_side) (void)hipEventDestroy(e->ev_side);
-  if (e->side) (void)hipStreamDestroy(e->side);
   delete e;
   return OGBX_OK;
 }
@@ -1572,22 +1422,20 @@ ogbx_status ogbx_powder_reset(ogbx_powder_t e, const int32_t* task_id, const uin
              OGBX_EINVAL, "injected rand needs task_id, reset_action and rand_rows >= longest task + 1");
   OGBX_HIP(hipSetDevice(e->device));
   e->seed = seed;
-  prep_invalidate(e);
-  e->order_ready = false;
   uint32_t k0, k1, r0, r1;
   seed_key(seed, kTagPowderReset, &k0, &k1);
   seed_key(seed, kTagPowderRand, &r0, &r1);
   if (e->full) {
-    PWF_LAUNCH(pwf_reset_kernel, e, (uint32_t)e->n, stream, e->Pd, e->S, task_id, mask, reset_action, rand,
+    PW_LAUNCH(pwf_reset_kernel, pwf_nt, e, (uint32_t)e->n, stream, e->Pd, e->S, task_id, mask, reset_action, rand,
               rand_rows, obs, goal_obs, k0, k1, r0, r1);
     OGBX_LAUNCHED("pwf_reset_kernel");
   } else {
-    PW_LAUNCH(pw_reset_kernel, e, (uint32_t)e->n, stream, e->Pd, e->S, e->goals, task_id, mask, reset_action,
+    PW_LAUNCH(pw_reset_kernel, pw_nt, e, (uint32_t)e->n, stream, e->Pd, e->S, e->goals, task_id, mask, reset_action,
               obs, goal_obs, k0, k1);
     OGBX_LAUNCHED("pw_reset_kernel");
   }
   e->was_reset = true;
-  e->phase = mask == nullptr ? 0 : -1;
+  pwf_schedule_reset(e->sched, mask == nullptr);
   return OGBX_OK;
 }
 
@@ -1606,103 +1454,34 @@ ogbx_status ogbx_powder_step(ogbx_powder_t e, const int32_t* action, int32_t k_s
   seed_key(e->seed, kTagPowderAction, &a0, &a1);
   seed_key(e->seed, kTagPowderRand, &r0, &r1);
   if (e->full) {
-    bool all_full = false;  // every in-phase env runs the full kernel this step
-    if (e->phase >= 0 && k_steps == 1) {
-      const int64_t T = e->P.max_steps > 0 ? e->P.max_steps : 0;
-      const int64_t j = (auto_reset && T > 0) ? e->phase % T : e->phase;  // the env's elapsed steps
-      all_full = j % 3 == 2 || (auto_reset && T > 0 && j + 1 >= T);
-    }
-    const bool light = e->light && k_steps == 1 && !all_full;
-    // prepared next-episode resets (PwPrep): in phase with auto-reset, one
-    // prepare launch of prep_ops replay ops on the side stream per render-only
-    // step until every env's reset is launched (the longest task: max_seq + 1
-    // ops); the synchronized reset step joins the side stream and loads them
-    const int64_t T = e->P.max_steps > 0 ? e->P.max_steps : 0;
-    const bool prep_on = e->prep_ops > 0 && e->side != nullptr && e->phase >= 0 && auto_reset && T > 0 &&
-                         k_steps == 1 && rand == nullptr && draws == nullptr;
-    ogbx::PwPrep prep = e->prep;
-    prep.use = 0;
-    bool sync_reset = false;
-    if (prep_on) {
-      const int64_t j = e->phase % T;
-      sync_reset = j + 1 >= T;
-      if (sync_reset && e->prep_launched >= e->max_seq + 1 && e->side_pending) {
-        OGBX_HIP(hipStreamWaitEvent((hipStream_t)stream, e->ev_side, 0));
-        e->side_pending = false;
-        prep.use = 1;
-      }
-    }
-    // fork before this render-only step's launches, so that the prepare may
-    // run beside them (it reads no state they write but ctrl's stage bits)
-    const bool prep_launch = prep_on && light && !sync_reset && e->prep_launched < e->max_seq + 1;
-    if (prep_launch) {
-      OGBX_HIP(hipEventRecord(e->ev_fork, (hipStream_t)stream));
-      OGBX_HIP(hipStreamWaitEvent(e->side, e->ev_fork, 0));
-    }
-    // the order of the next step's full launch, if the next step is an
-    // in-phase full step: sorted by a workgroup of this light launch
-    const bool had_order = e->order_ready;
-    const bool had_by_task = e->order_by_task;
-    e->order_ready = false;
-    int32_t order_mode = 0;
-    if (light && e->phase >= 0 && e->n <= INT32_MAX) {
-      const int64_t jn = (auto_reset && T > 0) ? (e->phase + 1) % T : e->phase + 1;
-      const bool sync_next = auto_reset && T > 0 && jn + 1 >= T;
-      if (jn % 3 == 2 || sync_next) order_mode = sync_next ? 2 : 1;
-    }
-    if (light) {
-      PW_LAUNCH(pwf_light_step_kernel, e, (uint32_t)e->n + (order_mode ? 1u : 0u), stream, e->Pd, e->S, action, draws,
-                obs, reward, terminated, truncated, success, auto_reset, a0, a1, e->handled, (int32_t)e->cache_stale,
-                order_mode, (int32_t)e->n, e->cost, e->order);
+    // the launches below, in their fixed order, each as the plan says (powder_schedule.h)
+    const PwfStepPlan p = pwf_plan_step(e->sched, e->P.max_steps, auto_reset, k_steps, e->light, e->n <= INT32_MAX);
+    if (p.light) {
+      PW_LAUNCH(pwf_light_step_kernel, pw_nt, e, (uint32_t)e->n + (p.order_mode ? 1u : 0u), stream, e->Pd, e->S,
+                action, draws, obs, reward, terminated, truncated, success, auto_reset, a0, a1, e->handled,
+                (int32_t)e->cache_stale, p.order_mode, (int32_t)e->n, e->cost, e->order);
       OGBX_LAUNCHED("pwf_light_step_kernel");
-      e->order_ready = order_mode != 0;
-      e->order_by_task = order_mode == 2;
     }
-    // in phase, a render-only step leaves (nearly) no env to the full kernel
-    if (light && e->phase >= 0) {
+    if (p.run_order_kernel) {
+      hipLaunchKernelGGL(pwf_order_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, e->Pd, e->S.ctrl, e->cost,
+                         (int32_t)e->n, (int32_t)p.by_task, e->order);
+      OGBX_LAUNCHED("pwf_order_kernel");
+    }
+    if (p.sparse) {
       const int32_t chunk = kPwfSparseChunk;
-      PWF_LAUNCH(pwf_step_kernel_sparse, e, (uint32_t)((e->n + chunk - 1) / chunk), stream, e->Pd, e->S, e->n,
-                 action, draws, rand, k_steps, obs, reward, terminated, truncated, success, auto_reset, k0, k1, a0,
-                 a1, r0, r1, e->handled, (int32_t)e->cache_stale, chunk, (const int32_t*)nullptr, (uint32_t*)nullptr,
-                 prep);
+      PW_LAUNCH(pwf_step_kernel_sparse, pwf_nt, e, (uint32_t)((e->n + chunk - 1) / chunk), stream, e->Pd, e->S, e->n,
+                action, draws, rand, k_steps, obs, reward, terminated, truncated, success, auto_reset, k0, k1, a0, a1,
+                r0, r1, e->handled, (int32_t)e->cache_stale, chunk, (const int32_t*)nullptr, (uint32_t*)nullptr);
     } else {
-      // in-phase full step: workgroups longest first (the synchronized goal
-      // replays by task length, forward steps by last measured cost)
-      const int32_t* order = nullptr;
-      if (all_full && e->n <= INT32_MAX) {
-        const int64_t T = e->P.max_steps > 0 ? e->P.max_steps : 0;
-        const int64_t j = (auto_reset && T > 0) ? e->phase % T : e->phase;
-        // a synchronized reset step replays by task length, unless it loads
-        // prepared states (then the forward-cost order)
-        const int32_t by_task = (auto_reset && T > 0 && j + 1 >= T && !prep.use) ? 1 : 0;
-        if (!(had_order && had_by_task == (by_task != 0))) {
-          hipLaunchKernelGGL(pwf_order_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, e->Pd, e->S.ctrl, e->cost,
-                             (int32_t)e->n, by_task, e->order);
-          OGBX_LAUNCHED("pwf_order_kernel");
-        }
-        order = e->order;
-      }
-      PWF_LAUNCH(pwf_step_kernel_dense, e, (uint32_t)e->n, stream, e->Pd, e->S, e->n, action, draws, rand, k_steps,
-                 obs, reward, terminated, truncated, success, auto_reset, k0, k1, a0, a1, r0, r1,
-                 light ? e->handled : (const uint8_t*)nullptr, (int32_t)e->cache_stale, 1, order, e->cost, prep);
+      PW_LAUNCH(pwf_step_kernel_dense, pwf_nt, e, (uint32_t)e->n, stream, e->Pd, e->S, e->n, action, draws, rand,
+                k_steps, obs, reward, terminated, truncated, success, auto_reset, k0, k1, a0, a1, r0, r1,
+                p.pass_skip ? e->handled : (const uint8_t*)nullptr, (int32_t)e->cache_stale, 1,
+                p.use_order ? e->order : (const int32_t*)nullptr, e->cost);
     }
     OGBX_LAUNCHED("pwf_step_kernel");
-    if (sync_reset) e->prep_launched = 0;  // the next episode's round starts
-    if (prep_launch) {
-      uint32_t pk0, pk1, pr0, pr1;
-      seed_key(e->seed, kTagPowderReset, &pk0, &pk1);
-      seed_key(e->seed, kTagPowderRand, &pr0, &pr1);
-      PWF_LAUNCH(pwf_prepare_kernel, e, (uint32_t)e->n, e->side, e->Pd, e->S, e->prep, e->prep_ops, pk0, pk1, pr0,
-                 pr1);
-      OGBX_LAUNCHED("pwf_prepare_kernel");
-      OGBX_HIP(hipEventRecord(e->ev_side, e->side));
-      e->side_pending = true;
-      e->prep_launched += e->prep_ops;
-    }
     e->cache_stale = false;  // every env's cache was written by one of the two kernels
-    if (e->phase >= 0) e->phase += k_steps;
   } else {
-    PW_LAUNCH(pw_step_kernel, e, (uint32_t)e->n, stream, e->Pd, e->S, e->goals, e->n, action, draws, k_steps, obs,
+    PW_LAUNCH(pw_step_kernel, pw_nt, e, (uint32_t)e->n, stream, e->Pd, e->S, e->goals, e->n, action, draws, k_steps, obs,
               reward, terminated, truncated, success, auto_reset, k0, k1, a0, a1);
     OGBX_LAUNCHED("pw_step_kernel");
   }
@@ -1736,21 +1515,20 @@ ogbx_status ogbx_powder_state_view(ogbx_powder_t e, const uint8_t** world, const
 ogbx_status ogbx_powder_state_written(ogbx_powder_t e) {
   OGBX_CHECK(e, OGBX_EINVAL, "null handle");
   e->cache_stale = true;
-  e->phase = -1;  // a restored state need not step in phase with the last reset
+  e->sched.phase = kPwfPhaseUnknown;  // a restored state need not step in phase with the last reset
   e->was_reset = true;
   return OGBX_OK;
 }
 
 ogbx_status ogbx_powder_set_phase(ogbx_powder_t e, int64_t phase) {
   OGBX_CHECK(e, OGBX_EINVAL, "null handle");
-  OGBX_CHECK(phase >= -1, OGBX_EINVAL, "phase must be >= -1");
-  e->phase = phase;
+  OGBX_CHECK(phase >= kPwfPhaseUnknown, OGBX_EINVAL, "phase must be >= -1");
+  e->sched.phase = phase;
   return OGBX_OK;
 }
 
 ogbx_status ogbx_powder_set_seed(ogbx_powder_t e, uint64_t seed) {
   OGBX_CHECK(e, OGBX_EINVAL, "null handle");
-  prep_invalidate(e);
   e->seed = seed;
   return OGBX_OK;
 }
@@ -1772,7 +1550,7 @@ ogbx_status ogbx_powder_forward(ogbx_powder_t e, const uint8_t* world_in, int64_
   OGBX_CHECK(!e->full, OGBX_EINVAL, "packed-byte forward is the easy element set; use ogbx_powder_forward_full");
   if (n_worlds == 0) return OGBX_OK;
   OGBX_HIP(hipSetDevice(e->device));
-  PW_LAUNCH(pw_forward_kernel, e, (uint32_t)n_worlds, stream, e->Pd, world_in, world_out, steps);
+  PW_LAUNCH(pw_forward_kernel, pw_nt, e, (uint32_t)n_worlds, stream, e->Pd, world_in, world_out, steps);
   OGBX_LAUNCHED("pw_forward_kernel");
   return OGBX_OK;
 }
@@ -1785,7 +1563,7 @@ ogbx_status ogbx_powder_forward_full(ogbx_powder_t e, const float* world_in, int
   OGBX_HIP(hipSetDevice(e->device));
   uint32_t r0, r1;
   seed_key(e->seed, kTagPowderRand, &r0, &r1);
-  PWF_LAUNCH(pwf_forward_kernel, e, (uint32_t)n_worlds, stream, e->Pd, world_in, n_worlds, steps, rand, world_out,
+  PW_LAUNCH(pwf_forward_kernel, pwf_nt, e, (uint32_t)n_worlds, stream, e->Pd, world_in, n_worlds, steps, rand, world_out,
             rgb_out, r0, r1);
   OGBX_LAUNCHED("pwf_forward_kernel");
   return OGBX_OK;

@@ -404,7 +404,7 @@ def test_kept_pointer_write_and_read_only_views(gpu):
 @pytest.mark.parametrize('ne,size', [(5, 64), (8, 32)])
 def test_out_of_phase_envs_after_full_reset_match_fused(gpu, ne, size):
     """A mixed-stage state loaded after an all-env reset: load_state_dict drops
-    the host's phase guess (ogbx_powder_env::phase), so every step launches the
+    the host's phase guess (PwfSchedule::phase), so every step launches the
     light kernel and the one-env full kernel; the steps must match the fused
     rollout from the same state bit for bit (a wrong guess:
     test_wrong_phase_hint_matches_fused)."""
@@ -477,37 +477,26 @@ def test_wrong_phase_hint_matches_fused(gpu, ne, size, phase):
 
 
 @pytest.mark.parametrize('ne', [5, 8])
-def test_prepared_resets_match_inline_replays(gpu, ne, monkeypatch):
-    """OGBX_PWF_PREP_OPS (off by default): next-episode reset
-    states prepared on the low-priority side stream and loaded by the
-    synchronized auto-reset step give exactly the in-line goal replays'
-    outputs and state, and the reset step loads instead of replaying."""
-    n, T, K = 8, 45, 100
-    monkeypatch.setenv('OGBX_PWF_PREP_OPS', '8')
-    a = _env(gpu, n, ne=ne, size=32, max_episode_steps=T, auto_reset=True)
-    monkeypatch.delenv('OGBX_PWF_PREP_OPS')
-    b = _env(gpu, n, ne=ne, size=32, max_episode_steps=T, auto_reset=True)
+def test_in_phase_steps_match_fused(gpu, ne):
+    """An in-phase batch with auto-reset stepped one call at a time, across two
+    synchronized resets (steps 6 and 13 of 18 at max_episode_steps=7) and
+    several forward steps: the light kernel with its pre-sorting workgroup,
+    then the dense full kernel in that order (by task length at the resets, by
+    last cost at the forwards).  Must match one fused rollout bit for bit."""
+    n, K = 8, 18
+    a = _env(gpu, n, ne=ne, size=32, max_episode_steps=7, auto_reset=True)
+    b = _env(gpu, n, ne=ne, size=32, max_episode_steps=7, auto_reset=True)
     opts = dict(task_id=torch.arange(n, device=gpu) % 5 + 1)
     a.reset(seed=11, options=opts)
     b.reset(seed=11, options=opts)
     rng = np.random.RandomState(2)
-    acts = torch.tensor(rng.randint(0, max(ne, a._xy_action_size), size=(K, n)), dtype=torch.int32, device=gpu)
-    ms = {}
+    acts = rng.randint(0, max(ne, a._xy_action_size), size=(K, n))
+    out = b.rollout(acts)
     for t in range(K):
-        outs = {}
-        for name, env in (('a', a), ('b', b)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            ob, rew, term, trunc, info = env.step(acts[t])
-            e1.record()
-            outs[name] = [x.clone() for x in (ob, rew, term, trunc, info['success'])]
-            if t == T - 1:
-                torch.cuda.synchronize()
-                ms[name] = e0.elapsed_time(e1)
-        for k, (x, y) in enumerate(zip(outs['a'], outs['b'])):
-            assert torch.equal(x, y), (t, k)
+        ob, rew, term, trunc, info = a.step(acts[t])
+        assert torch.equal(out['obs'][t], ob), t
+        assert torch.equal(out['reward'][t], rew), t
+        assert torch.equal(out['truncated'][t].bool(), trunc), t
     sa, sb = a.state_dict(), b.state_dict()
     for k in ('world', 'ctrl', 'elapsed', 'episode', 'momentum', 'velocity', 'goal'):
         assert torch.equal(sa[k], sb[k]), k
-    # the synchronized reset at step T-1 loaded prepared states (no replay)
-    assert ms['a'] < ms['b'] / 3, ms
