@@ -21,264 +21,13 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gc_device.h"
 #include "gc_select.h"
 
 namespace ogbx {
 
-constexpr int kGcMaxTile = 64;
-constexpr int kGcMaxCols = 32;
-
-template <int N>
-struct GcColumnsN {
-  ogbx_gc_column c[N];
-};
-using GcColumns = GcColumnsN<kGcMaxCols>;
-// A sampler plan's batches of at most 16 columns (GC 9, HGC 15) launch with
-// this half-size table: the host's launch cost grows with the kernel
-// arguments (a 1,376-byte argument 2.5 -> 3.4 us per launch on ROCm 7,
-// profiles/r06_launch_host.txt), and a steady sample(1024) call is host-bound.
-constexpr int kGcSmallCols = 16;
-using GcColumnsSmall = GcColumnsN<kGcSmallCols>;
-
-__device__ inline uint64_t bounded64(uint32_t hi, uint32_t lo, uint64_t n) {
-  const uint64_t u = ((uint64_t)hi << 32) | lo;
-  return __umul64hi(u, n);
-}
-
-struct GoalDraws {
-  int64_t pick;
-  int64_t geom;
-  double dist, u_traj, u_cur;
-};
-
-// GCDataset.sample_goals for one sample (datasets.py:296-327).
-// rand_goal = valid_idxs[d.pick] (or d.pick), loaded by the caller together
-// with the sample's other index loads.
-__device__ inline int64_t sample_goal(int64_t idx, int64_t final_idx, const GoalDraws& d,
-                                      int64_t rand_goal, double p_cur, double thresh, int geom,
-                                      int cur_is_one) {
-  if (cur_is_one) return idx;
-  int64_t traj;
-  if (geom) {
-    const int64_t s = idx + d.geom;
-    traj = s < final_idx ? s : final_idx;
-  } else {
-    const int64_t lo = idx + 1 < final_idx ? idx + 1 : final_idx;
-    traj = (int64_t)rint((double)lo * d.dist + (double)final_idx * (1.0 - d.dist));
-  }
-  int64_t goal = d.u_traj < thresh ? traj : rand_goal;
-  goal = d.u_cur < p_cur ? idx : goal;
-  return goal;
-}
-
-// The sample's dependent index loads, issued back to back so that they share
-// one HBM round trip: idx = valid_idxs[pick], its trajectory end, and the
-// random goals valid_idxs[goal pick] (datasets.py:65-70, 307-309).  Every
-// condition is wave-uniform (pointer presence), so no load address waits on
-// another load; for explicit idxs (pick < 0) the end needs idx first.
-// Periodic buffer (ogbx_gc_buffer.period > 0): pick p lies in period
-// q = p / period_picks at offset r, so idx = q period + r and its trajectory
-// end is q period + period_end -- no index load at all.  The IEEE quotient is
-// off by at most one near an integer; the remainder test corrects it.
-__device__ inline int64_t periodic_row(const ogbx_gc_buffer& buf, int64_t pick, int64_t* q_out) {
-  // the quotient estimate by the reciprocal (a function of the kernel
-  // arguments alone, so it is computed off the sample's chain): within one of
-  // floor(pick / period_picks) like the IEEE quotient, and the remainder test
-  // below makes q exact either way
-  const double inv_pp = 1.0 / (double)buf.period_picks;
-  int64_t q = (int64_t)((double)pick * inv_pp);
-  int64_t r = pick - q * buf.period_picks;
-  if (r < 0) {
-    --q;
-    r += buf.period_picks;
-  } else if (r >= buf.period_picks) {
-    ++q;
-    r -= buf.period_picks;
-  }
-  *q_out = q;
-  return q * buf.period + r;
-}
-
-__device__ inline void index_loads(const ogbx_gc_buffer& buf, bool explicit_idxs, int64_t pick,
-                                   int64_t* idx, int64_t* fin) {
-  const int64_t* __restrict__ vi = buf.valid_idxs;
-  if (!explicit_idxs && buf.period > 0) {
-    int64_t q;
-    *idx = periodic_row(buf, pick, &q);
-    *fin = q * buf.period + buf.period_end;
-  } else if (explicit_idxs) {
-    *fin = buf.traj_end[*idx];
-  } else if (buf.valid_pairs) {
-    const longlong2 p = reinterpret_cast<const longlong2*>(buf.valid_pairs)[pick];
-    *idx = p.x;
-    *fin = p.y;
-  } else if (vi && buf.valid_traj_end) {
-    *idx = vi[pick];
-    *fin = buf.valid_traj_end[pick];
-  } else if (vi) {
-    *idx = vi[pick];
-    *fin = buf.traj_end[*idx];
-  } else {
-    *idx = pick;
-    *fin = buf.traj_end[pick];
-  }
-}
-
-__device__ inline int64_t rand_goal_of(const ogbx_gc_buffer& buf, int64_t pick) {
-  if (buf.period > 0) {
-    int64_t q;
-    return periodic_row(buf, pick, &q);
-  }
-  if (buf.valid_pairs) return buf.valid_pairs[2 * pick];
-  return buf.valid_idxs ? buf.valid_idxs[pick] : pick;
-}
-
-// Source row pitch of a column in units of T (src_stride 0 = dense rows).
-template <typename T>
-__device__ __forceinline__ int64_t src_pitch(const ogbx_gc_column& col) {
-  return (col.src_stride ? (int64_t)col.src_stride : col.row_bytes) / (int64_t)sizeof(T);
-}
-
-__device__ inline int64_t geometric_from(double u, double log_q) {
-  // legacy RandomState.geometric inversion: ceil(log(1-u) / log(1-p))
-  double g = ceil(log(1.0 - u) / log_q);
-  return g < 1.0 ? 1 : (int64_t)g;
-}
-
-// Threads [t0, blockDim.x) copy (t0 = 64: the first wave is busy elsewhere).
-template <typename T>
-__device__ inline void copy_rows(const ogbx_gc_column& col, const int64_t* sel, int64_t base,
-                                 int tile, int t0) {
-  const int64_t units = col.row_bytes / (int64_t)sizeof(T);
-  const int64_t pitch = src_pitch<T>(col);
-  const T* __restrict__ src = (const T*)col.src;
-  T* __restrict__ dst = (T*)col.dst;
-  const int64_t total = units * tile;
-  const int step = blockDim.x - t0, tid = threadIdx.x - t0;
-  int64_t b = tid / units, k = tid % units;
-  const int64_t sb = step / units, sk = step % units;
-  for (int64_t f = tid; f < total; f += step) {
-    dst[(base + b) * units + k] = src[sel[b] * pitch + k];
-    k += sk;
-    b += sb;
-    if (k >= units) {
-      k -= units;
-      b += 1;
-    }
-  }
-}
-
-// Copy every column row of a tile.  For small tiles (latency-bound launches)
-// whose columns are all 4-byte granular with rows of <= 128 words, each
-// (column, sample) row is one job for one wave: the job's column descriptor
-// and row index are wave-uniform (scalar loads, one LDS broadcast), lanes
-// cover the row's words, and each wave issues the loads of up to kJ jobs
-// before any store, so all column rows of the tile share one HBM round trip.
-// Otherwise each column is copied with its widest aligned unit.
-// Waves [wave0, blockDim.x / 64) copy (wave0 = 1: the first wave computes the
-// next call's selectors meanwhile, gc_ahead_kernel).
-// kNt: non-temporal stores on the small-tile path (the HGC hit kernel: its 3.6
-// MB of rows per launch leave less to the end-of-kernel write-back, 6.44 ->
-// 6.34 us; GC's 1.3 MB measured 4.34 -> 4.38 us and keeps plain stores)
-template <int kSel, bool kNt = false, class Cols = GcColumns>
-__device__ inline void copy_tile(const Cols& cols, int num_cols, const int64_t (*sel)[kGcMaxTile], int64_t base,
-                                 int n_here, bool flat4, int wave0 = 0) {
-  if ((int)(threadIdx.x >> 6) < wave0) return;
-  if (flat4) {
-    constexpr int kJ = 8, kSlots = 2;
-    const int nw = (int)(blockDim.x >> 6) - wave0;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) - wave0;
-    const int lane = (int)(threadIdx.x & 63);
-    const int jobs = num_cols * n_here;
-    for (int j0 = wave; j0 < jobs; j0 += nw * kJ) {
-      uint32_t v[kJ][kSlots];
-      uint32_t* d[kJ][kSlots];
-#pragma unroll
-      for (int u = 0; u < kJ; ++u) {
-        const int j = j0 + u * nw;
-#pragma unroll
-        for (int q = 0; q < kSlots; ++q) d[u][q] = nullptr;
-        if (j < jobs) {
-          const int c = j / n_here, b = j - c * n_here;
-          const ogbx_gc_column& col = cols.c[c];
-          const int units = (int)(col.row_bytes >> 2);
-          const uint32_t* src = (const uint32_t*)col.src + sel[col.select][b] * src_pitch<uint32_t>(col);
-          uint32_t* dst = (uint32_t*)col.dst + (base + b) * units;
-#pragma unroll
-          for (int q = 0; q < kSlots; ++q) {
-            const int k = lane + 64 * q;
-            if (k < units) {
-              v[u][q] = src[k];
-              d[u][q] = dst + k;
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kJ; ++u)
-#pragma unroll
-        for (int q = 0; q < kSlots; ++q)
-          if (d[u][q]) {
-            if constexpr (kNt)
-              __builtin_nontemporal_store(v[u][q], d[u][q]);
-            else
-              *d[u][q] = v[u][q];
-          }
-    }
-    return;
-  }
-  for (int c = 0; c < num_cols; ++c) {
-    const ogbx_gc_column& col = cols.c[c];
-    const int64_t* srow = sel[col.select];
-    const uintptr_t align = (uintptr_t)col.src | (uintptr_t)col.dst | (uintptr_t)col.src_stride;
-    const int t0 = 64 * wave0;
-    if (col.row_bytes % 16 == 0 && align % 16 == 0)
-      copy_rows<uint4>(col, srow, base, n_here, t0);
-    else if (col.row_bytes % 8 == 0 && align % 8 == 0)
-      copy_rows<uint2>(col, srow, base, n_here, t0);
-    else if (col.row_bytes % 4 == 0 && align % 4 == 0)
-      copy_rows<uint32_t>(col, srow, base, n_here, t0);
-    else
-      copy_rows<uint8_t>(col, srow, base, n_here, t0);
-  }
-}
-
-// The tile's Philox words, one call per lane: sample b of the tile, call q
-// (q < calls) -> wb[q][b].  A B = 1024 launch has two samples per workgroup,
-// so in-lane calls would run kCalls dependent-free chains on two lanes; spread
-// over 2 * kCalls lanes each lane runs one.  Same counters and keys as the
-// in-lane form, so the words are identical.
-constexpr bool kGcSpread = true;
-// Every lane of a wave that has a call computes one (lanes past the last call
-// repeat one and store nothing): gfx950 issues a dependent integer chain about
-// twice as slowly with <= 16 active lanes, and a B = 1,024 tile
-// has 5-7 calls.
-__device__ inline void tile_philox(uint4 (*wb)[kGcMaxTile], int calls, int n_here, int64_t base,
-                                   uint32_t call_lo, uint32_t call_hi, uint32_t k0, uint32_t k1) {
-  const int tot = calls * n_here, span = (tot + 63) & ~63;
-  for (int t = threadIdx.x; t < span; t += blockDim.x) {
-    const int tt = t < tot ? t : t % tot;
-    const int b = tt / calls, q = tt - b * calls;
-    const uint64_t su = (uint64_t)(base + b);
-    const u32x4 w = philox4x32_10({(uint32_t)su, call_lo, (uint32_t)q, (uint32_t)(su >> 32) ^ call_hi}, k0, k1);
-    if (t < tot) wb[q][b] = make_uint4(w.x, w.y, w.z, w.w);
-  }
-}
-// Tile of this workgroup: consecutive workgroup ids go round-robin to the 8
-// XCDs, each with its own L2, so tiles are numbered XCD-major -- the
-// workgroups of one XCD own a contiguous run of samples and the partial
-// 128-B lines where one sample's output rows meet the next are merged in
-// that XCD's L2 instead of being written back twice.
-__device__ inline int64_t xcd_tile() {
-  const int64_t b = blockIdx.x, nb = gridDim.x;
-  const int64_t per = nb >> 3, rem = nb & 7, x = b & 7;
-  return x * per + (x < rem ? x : rem) + (b >> 3);
-}
-
-__device__ inline u32x4 tile_word(const uint4 (*wb)[kGcMaxTile], int q, int b) {
-  const uint4 v = wb[q][b];
-  return u32x4{v.x, v.y, v.z, v.w};
-}
+// The draw chain, the tile helpers and the shared argument checks: gc_device.h
+// (trl.hip builds its kernel from the same pieces).
 
 template <bool kInj>
 __global__ void __launch_bounds__(256) gc_sample_kernel(
@@ -919,70 +668,6 @@ struct PositiveF32 {
 
 using namespace ogbx;
 
-// Every column 4-byte granular and aligned with rows of <= 128 words (the
-// per-wave job copy of copy_tile).
-static bool flat4_columns(const GcColumns& cc, int num_cols) {
-  for (int i = 0; i < num_cols; ++i) {
-    const ogbx_gc_column& c = cc.c[i];
-    if (c.row_bytes % 4 != 0 || c.row_bytes > 512 ||
-        ((uintptr_t)c.src | (uintptr_t)c.dst | (uintptr_t)c.src_stride) % 4 != 0)
-      return false;
-  }
-  return true;
-}
-
-// True when any draw is injected (parity replays); the Philox-only kernels
-// carry no per-draw pointer tests, so their index loads issue back to back.
-static bool any_draw(const ogbx_gc_draws& d) {
-  return d.idxs || d.pick || d.v_pick || d.v_geom || d.v_dist || d.v_u_traj || d.v_u_cur ||
-         d.a_pick || d.a_geom || d.a_dist || d.a_u_traj || d.a_u_cur;
-}
-
-// period == 0, or a whole number of periods covering the buffer with the
-// picks and the trajectory end inside one period.
-static bool periodic_ok(const ogbx_gc_buffer& b) {
-  if (b.period == 0) return true;
-  const int64_t npick = b.valid_idxs ? b.num_valid : b.num_rows;
-  return b.period > 0 && b.period_picks > 0 && b.period_picks <= b.period && b.period_end >= 0 &&
-         b.period_end < b.period && b.num_rows % b.period == 0 &&
-         npick == (b.num_rows / b.period) * b.period_picks;
-}
-
-// ------------------------------------------------------------ argument checks
-// Every check of the GC / HGC entry points lives here, once; an entry point
-// runs its checks before its first HIP call.  `who` is the entry point's name.
-#define GC_TRY(expr)                       \
-  do {                                     \
-    if (ogbx_status _st = (expr)) return _st; \
-  } while (0)
-
-static std::string named(const char* who, const char* what) { return std::string(who) + ": " + what; }
-
-static ogbx_status check_buffer(const ogbx_gc_buffer* buf) {
-  OGBX_CHECK(buf->num_rows > 0 && buf->traj_end, OGBX_EINVAL, "empty trajectory buffer");
-  OGBX_CHECK(buf->valid_idxs == nullptr || buf->num_valid > 0, OGBX_EINVAL,
-             "no valid transitions in the dataset");
-  OGBX_CHECK(periodic_ok(*buf), OGBX_EINVAL, "ogbx_gc_buffer: inconsistent period fields");
-  return OGBX_OK;
-}
-
-// The batch shape and the column descriptors (select in [0, max_select]),
-// copied into the kernel-argument table *cc.
-static ogbx_status check_columns(const ogbx_gc_column* cols, int32_t num_cols, int64_t batch, int64_t num_batches,
-                                 int max_select, const char* who, GcColumns* cc) {
-  OGBX_CHECK(num_cols >= 0 && num_cols <= kGcMaxCols, OGBX_EINVAL, named(who, "at most 32 columns"));
-  OGBX_CHECK(batch > 0 && num_batches > 0, OGBX_EINVAL, "batch and num_batches must be > 0");
-  for (int i = 0; i < num_cols; ++i) {
-    const ogbx_gc_column& c = cols[i];
-    OGBX_CHECK(c.src_stride == 0 || c.src_stride >= c.row_bytes, OGBX_EINVAL,
-               named(who, "src_stride below row_bytes"));
-    OGBX_CHECK(c.src && c.dst && c.row_bytes > 0 && c.select >= 0 && c.select <= max_select, OGBX_EINVAL,
-               named(who, "bad column descriptor"));
-    cc->c[i] = c;
-  }
-  return OGBX_OK;
-}
-
 // The look-ahead kernels run one sample per workgroup and read one selector
 // buffer while they write the other.
 static ogbx_status check_ahead(int64_t total, const int64_t* ahead_in, const int64_t* ahead_out, const char* who) {
@@ -1009,28 +694,6 @@ static ogbx_status check_hgc_outputs(const ogbx_hgc_outputs* out, const char* wh
                  out->low_value_rewards && out->masks && out->rewards,
              OGBX_EINVAL, named(who, "missing scalar output"));
   return OGBX_OK;
-}
-
-// ------------------------------------------------- derived launch parameters
-// tile: one sample per workgroup up to 1024 samples (B = 1024: 1,024
-// workgroups of 256 threads; measured against 2 and 4 samples per workgroup
-// and 64- to 1024-thread workgroups), then up to 64 per workgroup
-static int64_t gc_tile(int64_t total) { return std::clamp<int64_t>(total / 1024, 1, kGcMaxTile); }
-
-// What a (seed, config) fixes for every call: the Philox key and the
-// log(1 - p) terms of the geometric draws (p = 1 - discount).
-struct GcParams {
-  uint32_t k0 = 0, k1 = 0;
-  double v_log_q = 0, a_log_q = 0, l_log_q = 0;
-};
-
-static GcParams gc_params(uint64_t seed, const ogbx_gc_config& cfg, const ogbx_hgc_config* hcfg) {
-  GcParams pr;
-  seed_key(seed, hcfg ? kTagHgcSample : kTagGcSample, &pr.k0, &pr.k1);
-  pr.v_log_q = std::log(1.0 - (1.0 - cfg.value_discount));
-  pr.a_log_q = std::log(1.0 - (1.0 - cfg.actor_discount));
-  pr.l_log_q = (hcfg && hcfg->has_low_value_goals) ? std::log(1.0 - (1.0 - hcfg->low_discount)) : 0.0;
-  return pr;
 }
 
 // GC per-sample scalar outputs (the index outputs may be NULL).

@@ -1,0 +1,220 @@
+// trl.hip -- TRL batches of GCDataset on gfx950 (include/ogbx_trl.h): the
+// GC sample chain plus the value midpoint, a row drawn uniformly between the
+// sample and its value goal, and the gathers of every column in one launch.
+//
+// Reference (hliuson/ogbench impls/utils/datasets.py):
+//   GCDataset.__post_init__, TRL pick table   198-204
+//   GCDataset.sample, TRL branch              254-292
+//
+// trl_sample_kernel is organised as gc_sample_kernel (gcsample.hip) and built
+// from the same device code (gc_device.h): tiles of at most 64 samples
+// numbered XCD-major, the first wave runs the draw chain into LDS selectors,
+// then the whole workgroup copies rows.  The fifth selector, the midpoint, is
+// arithmetic on idx and the value goal -- mid = idx + mulhi(u64, goal - idx)
+// with the two Philox words of slot 4 that the GC chain leaves unused -- so it
+// adds no dependent load: midpoint rows are fetched in the same round trip as
+// goal rows.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include "../../include/ogbx_trl.h"
+#include "common.h"
+#include "gc_device.h"
+
+namespace ogbx {
+
+constexpr int kTrlSel = OGBX_TRL_SELECT_MIDPOINT + 1;
+
+template <bool kInj>
+__global__ void __launch_bounds__(256) trl_sample_kernel(
+    ogbx_gc_buffer buf, ogbx_gc_config cfg, GcColumns cols, int32_t num_cols, int64_t total, int tile,
+    ogbx_gc_draws dr, const int64_t* __restrict__ mid_in, uint32_t k0, uint32_t k1, uint32_t call_lo,
+    uint32_t call_hi, double v_log_q, double a_log_q, ogbx_trl_outputs o, ogbx_gc_draw_record rec,
+    int64_t* __restrict__ mid_rec, bool flat4) {
+  __shared__ int64_t sel[kTrlSel][kGcMaxTile];
+  __shared__ uint4 wb[(!kInj && kGcSpread) ? 5 : 1][kGcMaxTile];
+  const int64_t base = xcd_tile() * tile;
+  const int n_here = (int)((total - base) < tile ? (total - base) : tile);
+  if (!kInj && kGcSpread) {
+    tile_philox(wb, 5, n_here, base, call_lo, call_hi, k0, k1);
+    __syncthreads();
+  }
+  if (threadIdx.x < 64 && n_here > 0) {  // the whole first wave: see gc_sample_kernel
+    const int b = (int)threadIdx.x % n_here;
+    const bool own = (int)threadIdx.x < n_here;
+    const int64_t s = base + b;
+    const uint64_t su = (uint64_t)s;
+    const uint32_t c0 = (uint32_t)su, c3 = (uint32_t)(su >> 32) ^ call_hi;
+    u32x4 w0, w1, w2, w3, w4;
+    if (!kInj && kGcSpread) {
+      w0 = tile_word(wb, 0, b), w1 = tile_word(wb, 1, b), w2 = tile_word(wb, 2, b), w3 = tile_word(wb, 3, b),
+      w4 = tile_word(wb, 4, b);
+    } else {
+      w0 = philox4x32_10({c0, call_lo, 0u, c3}, k0, k1);
+      w1 = philox4x32_10({c0, call_lo, 1u, c3}, k0, k1);
+      w2 = philox4x32_10({c0, call_lo, 2u, c3}, k0, k1);
+      w3 = philox4x32_10({c0, call_lo, 3u, c3}, k0, k1);
+      w4 = philox4x32_10({c0, call_lo, 4u, c3}, k0, k1);
+    }
+    // the GC chain, word for word as gc_sample_kernel draws it
+    const int64_t npick = buf.valid_idxs ? buf.num_valid : buf.num_rows;
+    int64_t idx = 0, pick = -1, final_idx;
+    if (kInj && dr.idxs) idx = dr.idxs[s];
+    else pick = (kInj && dr.pick) ? dr.pick[s] : (int64_t)bounded64(w0.x, w0.y, (uint64_t)npick);
+    GoalDraws v, a;
+    v.pick = (kInj && dr.v_pick) ? dr.v_pick[s] : (int64_t)bounded64(w0.z, w0.w, (uint64_t)npick);
+    a.pick = (kInj && dr.a_pick) ? dr.a_pick[s] : (int64_t)bounded64(w1.x, w1.y, (uint64_t)npick);
+    // an injected midpoint row: loaded with the index loads, not after them
+    const int64_t mid_given = (kInj && mid_in) ? mid_in[s] : 0;
+    index_loads(buf, kInj && dr.idxs != nullptr, pick, &idx, &final_idx);
+    const int64_t v_rand = cfg.value_cur_is_one ? 0 : rand_goal_of(buf, v.pick);
+    const int64_t a_rand = cfg.actor_cur_is_one ? 0 : rand_goal_of(buf, a.pick);
+    const int64_t next = idx + 1 < buf.num_rows ? idx + 1 : buf.num_rows - 1;
+    const double uvg = u01_from(w1.z, w1.w), uag = u01_from(w2.x, w2.y);
+    v.geom = (kInj && dr.v_geom) ? dr.v_geom[s] : (cfg.value_geom_sample ? geometric_from(uvg, v_log_q) : 0);
+    a.geom = (kInj && dr.a_geom) ? dr.a_geom[s] : (cfg.actor_geom_sample ? geometric_from(uag, a_log_q) : 0);
+    v.dist = (kInj && dr.v_dist) ? dr.v_dist[s] : uvg;
+    a.dist = (kInj && dr.a_dist) ? dr.a_dist[s] : uag;
+    v.u_traj = (kInj && dr.v_u_traj) ? dr.v_u_traj[s] : u01_from(w2.z, w2.w);
+    v.u_cur = (kInj && dr.v_u_cur) ? dr.v_u_cur[s] : u01_from(w3.x, w3.y);
+    a.u_traj = (kInj && dr.a_u_traj) ? dr.a_u_traj[s] : u01_from(w3.z, w3.w);
+    a.u_cur = (kInj && dr.a_u_cur) ? dr.a_u_cur[s] : u01_from(w4.x, w4.y);
+    const int64_t vg = sample_goal(idx, final_idx, v, v_rand, cfg.value_p_curgoal,
+                                   cfg.value_traj_thresh, cfg.value_geom_sample, cfg.value_cur_is_one);
+    const int64_t ag = sample_goal(idx, final_idx, a, a_rand, cfg.actor_p_curgoal,
+                                   cfg.actor_traj_thresh, cfg.actor_geom_sample, cfg.actor_cur_is_one);
+    // value midpoint: randint(idx, vg) (datasets.py:259), words z, w of slot 4.
+    // No row lies in [idx, vg) when vg <= idx: counted, and mid = idx keeps
+    // the gathers inside the buffer.
+    const int64_t span = vg - idx;
+    const bool bad = span <= 0;
+    int64_t mid = idx;
+    if (!bad) {
+      if (kInj && mid_in)
+        mid = mid_given < 0 ? 0 : (mid_given >= buf.num_rows ? buf.num_rows - 1 : mid_given);
+      else
+        mid = idx + (int64_t)bounded64(w4.z, w4.w, (uint64_t)span);
+    }
+    if (o.bad_count) {  // every lane of the wave is here: one atomic per tile at most
+      const unsigned long long m = __ballot(bad && own);
+      if (m != 0ull && threadIdx.x == 0)
+        atomicAdd(reinterpret_cast<unsigned long long*>(o.bad_count), (unsigned long long)__popcll(m));
+    }
+    if (own) {
+    sel[0][b] = idx;
+    sel[1][b] = next;
+    sel[2][b] = vg;
+    sel[3][b] = ag;
+    sel[4][b] = mid;
+    if (o.idxs) o.idxs[s] = idx;
+    if (o.value_goal_idxs) o.value_goal_idxs[s] = vg;
+    if (o.actor_goal_idxs) o.actor_goal_idxs[s] = ag;
+    if (o.value_midpoint_idxs) o.value_midpoint_idxs[s] = mid;
+    if (o.value_offsets) o.value_offsets[s] = span;
+    if (o.value_midpoint_offsets) o.value_midpoint_offsets[s] = mid - idx;
+    const double succ = idx == vg ? 1.0 : 0.0;
+    if (o.masks) o.masks[s] = 1.0 - succ;
+    if (o.rewards) o.rewards[s] = succ - (cfg.gc_negative ? 1.0 : 0.0);
+    if (mid_rec) mid_rec[s] = mid;
+    if (rec.pick) {
+      rec.pick[s] = pick;
+      rec.v_pick[s] = v.pick;
+      rec.v_geom[s] = v.geom;
+      rec.v_dist[s] = v.dist;
+      rec.v_u_traj[s] = v.u_traj;
+      rec.v_u_cur[s] = v.u_cur;
+      rec.a_pick[s] = a.pick;
+      rec.a_geom[s] = a.geom;
+      rec.a_dist[s] = a.dist;
+      rec.a_u_traj[s] = a.u_traj;
+      rec.a_u_cur[s] = a.u_cur;
+    }
+    }  // own
+  }
+  __syncthreads();
+  copy_tile<0>(cols, num_cols, sel, base, n_here, flat4);
+}
+
+struct NotTrajEnd {
+  const int64_t* traj_end;
+  __device__ bool operator()(const int64_t& r) const { return traj_end[r] != r; }
+};
+
+// Device memory of `device`?
+static bool trl_on_device(const void* ptr, int device) {
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return attr.type == hipMemoryTypeDevice && attr.device == device;
+}
+
+}  // namespace ogbx
+
+using namespace ogbx;
+
+extern "C" {
+
+int32_t ogbx_trl_api_version(void) { return OGBX_TRL_API_VERSION; }
+
+ogbx_status ogbx_trl_sample(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg,
+                            const ogbx_gc_column* cols, int32_t num_cols, int64_t batch,
+                            int64_t num_batches, const ogbx_gc_draws* draws, const int64_t* midpoint,
+                            uint64_t seed, uint64_t call_index, const ogbx_trl_outputs* out,
+                            const ogbx_gc_draw_record* record, int64_t* midpoint_record, void* stream) {
+  const char* who = "ogbx_trl_sample";
+  OGBX_CHECK(buf && cfg && out && (cols || num_cols == 0), OGBX_EINVAL, named(who, "null argument"));
+  GcColumns cc{};
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, OGBX_TRL_SELECT_MIDPOINT, who, &cc));
+  GC_TRY(check_buffer(buf));
+  const ogbx_gc_draws dr = draws ? *draws : ogbx_gc_draws{};
+  const ogbx_gc_draw_record rec = record ? *record : ogbx_gc_draw_record{};
+  OGBX_CHECK(!rec.pick || (rec.v_pick && rec.v_geom && rec.v_dist && rec.v_u_traj && rec.v_u_cur && rec.a_pick &&
+                           rec.a_geom && rec.a_dist && rec.a_u_traj && rec.a_u_cur),
+             OGBX_EINVAL, named(who, "incomplete draw record"));
+
+  int dev = 0;
+  OGBX_HIP(hipGetDevice(&dev));
+  bool ok = trl_on_device(buf->traj_end, dev);
+  const void* opt[] = {buf->valid_idxs, buf->valid_traj_end, buf->valid_pairs, midpoint, midpoint_record,
+                       dr.idxs, dr.pick, dr.v_pick, dr.v_geom, dr.v_dist, dr.v_u_traj, dr.v_u_cur, dr.a_pick,
+                       dr.a_geom, dr.a_dist, dr.a_u_traj, dr.a_u_cur, rec.pick, rec.v_pick, rec.v_geom,
+                       rec.v_dist, rec.v_u_traj, rec.v_u_cur, rec.a_pick, rec.a_geom, rec.a_dist, rec.a_u_traj,
+                       rec.a_u_cur, out->idxs, out->value_goal_idxs, out->actor_goal_idxs,
+                       out->value_midpoint_idxs, out->value_offsets, out->value_midpoint_offsets, out->masks,
+                       out->rewards, out->bad_count};
+  for (const void* q : opt) ok = ok && (!q || trl_on_device(q, dev));
+  for (int i = 0; i < num_cols; ++i) ok = ok && trl_on_device(cols[i].src, dev) && trl_on_device(cols[i].dst, dev);
+  OGBX_CHECK(ok, OGBX_EINVAL, named(who, "every pointer must be device memory of the current device"));
+
+  const GcParams pr = gc_params(seed, *cfg, nullptr);  // the GC stream tag: same words as ogbx_gc_sample
+  const int64_t total = batch * num_batches;
+  const int64_t tile = gc_tile(total), blocks = (total + tile - 1) / tile;
+  const bool flat4 = tile <= 4 && flat4_columns(cc, num_cols);
+  const auto kern = (any_draw(dr) || midpoint) ? trl_sample_kernel<true> : trl_sample_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, *buf, *cfg, cc, num_cols,
+                     total, (int)tile, dr, midpoint, pr.k0, pr.k1, (uint32_t)call_index,
+                     (uint32_t)(call_index >> 32), pr.v_log_q, pr.a_log_q, *out, rec, midpoint_record, flat4);
+  OGBX_LAUNCHED("trl_sample_kernel");
+  return OGBX_OK;
+}
+
+ogbx_status ogbx_trl_valid_idxs(const int64_t* traj_end, int64_t num_rows, int64_t* out, int64_t* count,
+                                void* stream) {
+  OGBX_CHECK(traj_end && out && count && num_rows > 0, OGBX_EINVAL, "ogbx_trl_valid_idxs: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  hipcub::CountingInputIterator<int64_t> it(0);
+  NotTrajEnd pred{traj_end};
+  size_t tmp_bytes = 0;
+  OGBX_HIP(hipcub::DeviceSelect::If(nullptr, tmp_bytes, it, out, count, num_rows, pred, s));
+  void* tmp = nullptr;
+  OGBX_HIP(hipMallocAsync(&tmp, tmp_bytes > 0 ? tmp_bytes : 1, s));
+  hipError_t e = hipcub::DeviceSelect::If(tmp, tmp_bytes, it, out, count, num_rows, pred, s);
+  hipError_t e2 = hipFreeAsync(tmp, s);
+  if (e != hipSuccess) return hip_fail(e, "hipcub::DeviceSelect::If");
+  if (e2 != hipSuccess) return hip_fail(e2, "hipFreeAsync");
+  return OGBX_OK;
+}
+
+}  // extern "C"

@@ -156,6 +156,19 @@ class VisualIndices(ctypes.Structure):
 
 CROP_PADDING = 3  # GCDataset.augment (datasets.py:331)
 
+# the agents whose GCDataset batches carry the value-midpoint keys (datasets.py:198, 254)
+TRL_AGENTS = ('trl', 'latent_trl', 'discrete_latent_trl')
+_TRL_SCALARS = ('idxs', 'value_goal_idxs', 'actor_goal_idxs', 'value_midpoint_idxs', 'value_offsets',
+                'value_midpoint_offsets', 'masks', 'rewards', 'bad_count')
+# the observation-valued keys of the TRL branch, all in its augment list (datasets.py:283-290)
+_TRL_IMAGE_KEYS = ('value_goal_observations', 'actor_goal_observations', 'value_midpoint_observations',
+                   'value_midpoint_goals', 'value_cur_goals', 'value_next_goals')
+TRL_SELECT_MIDPOINT = 4  # OGBX_TRL_SELECT_MIDPOINT
+
+
+class TrlOutputs(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in _TRL_SCALARS]
+
 
 def _bind():
     L = _lib.lib()
@@ -201,6 +214,18 @@ def _bind():
             ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64,
             ctypes.c_void_p, ctypes.c_void_p,
         ]
+        # include/ogbx_trl.h (likewise its own header and version)
+        L.ogbx_trl_api_version.restype = ctypes.c_int32
+        L.ogbx_trl_api_version.argtypes = []
+        L.ogbx_trl_sample.restype = ctypes.c_int32
+        L.ogbx_trl_sample.argtypes = [
+            P(GcBuffer), P(GcConfig), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, P(GcDraws),
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, P(TrlOutputs), P(GcDrawRecord), ctypes.c_void_p,
+            ctypes.c_void_p,
+        ]
+        L.ogbx_trl_valid_idxs.restype = ctypes.c_int32
+        L.ogbx_trl_valid_idxs.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p]
         L._gc_bound = True
     return L
 
@@ -367,11 +392,57 @@ class GCDataset:
     it does not use the look-ahead plan.  Its non-image keys and indices are
     those of the same sampler without ``frame_stack`` / ``p_aug`` at the same
     seed and call.
+
+    TRL samplers.  With ``config['agent_name']`` in ``TRL_AGENTS`` a batch
+    also carries the keys of the reference's TRL branch (datasets.py:254-276),
+    built around the *value midpoint*, a row drawn uniformly in
+    [idx, value goal): ``value_goal_observations``, ``actor_goal_observations``
+    (both at the value goal, as the reference), ``value_offsets``,
+    ``value_midpoint_offsets`` (int64), ``value_midpoint_observations``,
+    ``value_midpoint_actions``, ``next_actions``, ``value_midpoint_goals``,
+    ``value_cur_goals`` and ``value_next_goals``, in the reference's order.
+    One launch of ``trl_sample_kernel`` (``ogbx_trl_sample``,
+    include/ogbx_trl.h) draws and gathers all of it; there is no look-ahead
+    plan for it.  ``idxs``, the goals, ``masks``, ``rewards`` and the nine GC
+    keys are those of a non-TRL sampler over the same pick table at the same
+    seed and call.  The config needs ``value_p_curgoal == 0`` and
+    ``value_p_randomgoal == 0`` (ValueError otherwise: the reference then
+    fails data-dependently, by its assert or by ``randint(low >= high)``).
+    Differences from the reference, both deliberate:
+
+    * the pick table -- every row but the last of its trajectory, whether or
+      not the dataset has 'valids' (datasets.py:198-204) -- is the sampler's
+      own (``_valid``); the reference overwrites ``dataset.valid_idxs``, here
+      the shared ``Dataset`` is left as it was;
+    * keys the reference computes by the same expression hold ONE tensor, and
+      each distinct (source, selector) is gathered once:
+      ``actor_goal_observations is value_goal_observations``; without
+      ``oracle_reps`` also ``value_cur_goals is observations``,
+      ``value_next_goals is next_observations`` (compact datasets; a regular
+      one stores its own ``next_observations``),
+      ``value_midpoint_goals is value_midpoint_observations`` and
+      ``value_goal_observations is value_goals``; with ``oracle_reps``,
+      ``value_goals`` (representations) and ``value_goal_observations``
+      (observations) are distinct and ``value_cur_goals is oracle_reps``.
+
+    ``next_actions`` / ``value_next_goals`` select min(idx + 1, R - 1), which is
+    idx + 1 for every pickable row.  Explicit ``idxs`` that name a
+    trajectory's last row (or injected draws with a value goal at or before
+    the sample) raise ValueError with the count of such samples, read back
+    after the launch; the Philox path reads nothing back.  ``draws`` takes
+    ``'midpoint'`` (the rows of the reference's ``randint(idxs,
+    value_goal_idxs)``), ``record_draws`` reports it with
+    ``_value_midpoint_idxs``.  A visual TRL sampler runs the fused launch, one
+    ``ogbx_visual_gather`` over the image columns at idx / next / goals and one
+    over those at the midpoint, which share the sample's crop offsets; the six
+    observation-valued TRL keys are stacked and cropped like
+    ``observations`` unless they come from ``oracle_reps``.
     """
 
     # the keys a visual sampler may stack, and of those the ones augment() crops
     _VISUAL_KEYS = ('observations', 'next_observations', 'value_goals', 'actor_goals')
     _CROP_KEYS = _VISUAL_KEYS
+    _TRL_OK = True  # the reference's GCDataset.sample has the TRL branch; HGCDataset.sample has none
 
     def __init__(self, dataset, config, preprocess_frame_stack=True, seed=None, _plain=False):
         torch = _torch()
@@ -388,8 +459,22 @@ class GCDataset:
             # only compact (observation-only) datasets (datasets.py:206-208)
             assert 'next_observations' not in dataset
             assert 1 <= self._frame_stack <= 8 and dataset['observations'].dim() >= 2
-        if config.get('agent_name') in ('trl', 'latent_trl', 'discrete_latent_trl'):
-            raise NotImplementedError('the TRL sampling branches are out of scope')
+        self._trl = not _plain and config.get('agent_name') in TRL_AGENTS
+        if self._trl:
+            if not self._TRL_OK:
+                raise NotImplementedError(f'{type(self).__name__}.sample has no TRL branch (nor has the reference)')
+            # any other setting lets a value goal fall on or before its sample,
+            # where the reference fails by its assert or by randint(low >= high)
+            if config['value_p_curgoal'] != 0 or config['value_p_randomgoal'] != 0:
+                raise ValueError('a TRL agent needs value_p_curgoal == 0 and value_p_randomgoal == 0 '
+                                 '(the value goal must lie past the sample in its trajectory)')
+            self._VISUAL_KEYS = self._CROP_KEYS = type(self)._VISUAL_KEYS + _TRL_IMAGE_KEYS
+            # a TRL sampler's sample() is bound here, on the instance, and not
+            # tested for inside sample(): a steady GC / HGC refill is bounded by
+            # host time, and one more attribute test per call measured 12 ns of
+            # HGCDataset.sample(1024)'s 6.40 us (profiles/trl_sampler.json,
+            # earlier_parent_comparisons.first_attempt)
+            self.sample = self._sample_trl_call
         L = _bind()
         self._L = L
         stream = _lib.stream_of(self.device)
@@ -412,6 +497,11 @@ class GCDataset:
         else:
             self.traj_end.fill_(self.size - 1)
         valid = getattr(dataset, 'valid_idxs', None)
+        if self._trl:
+            # the TRL pick table: every row but the last of its trajectory,
+            # with or without 'valids' (datasets.py:198-204); the sampler's
+            # own, the shared Dataset keeps its valid_idxs
+            valid = self._trl_valid_idxs(stream)
         # trajectory end of every valid row: the drawn index and its end load in parallel
         self.valid_traj_end = self.traj_end[valid].contiguous() if valid is not None else None
         # (index, trajectory end) of every valid row interleaved: one 16-B load per pick
@@ -458,6 +548,7 @@ class GCDataset:
         self._visual = not _plain and (fs is not None or (self._p_aug_live and any(
             dataset[k].dim() == 4 for k in ('observations', 'next_observations') if k in dataset)))
         self._vis_cache = {}
+        self._trl_cache = {}
         self._dev_idx = self.device.index
         self._plan_sample = L.ogbx_gc_plan_sample
         self._raw_stream = torch._C._cuda_getCurrentRawStream  # hipStream_t of the current stream, as an int
@@ -701,7 +792,9 @@ class GCDataset:
         for HGCDataset also the low-level ``l_*`` draws; device or host arrays
         of length num_batches*batch_size).  A visual sampler also takes
         ``'crop_from'``, the [num_batches*batch_size, 2] offsets (cy, cx) of
-        augment()'s randint (datasets.py:333), used when the call crops.
+        augment()'s randint (datasets.py:333), used when the call crops; a TRL
+        sampler ``'midpoint'``, the rows of randint(idxs, value_goal_idxs)
+        (datasets.py:259).
         record_draws: also return the draws the kernel used (``out['_draws']``;
         with ``'crop_from'`` on a call that cropped, and without it otherwise).
         num_batches > 1: sample that many independent batches in the same launch
@@ -828,6 +921,167 @@ class GCDataset:
             out.update({'_draws': rec_t, **idx_t})
         return out
 
+    # --------------------------------------------------------------- TRL batches
+    def _trl_valid_idxs(self, stream):
+        """Every row that is not the last of its trajectory, in order
+        (datasets.py:198-204), compacted on the device from ``traj_end``."""
+        torch = _torch()
+        rows = torch.empty(self.size, dtype=torch.int64, device=self.device)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+        _lib.check(self._L.ogbx_trl_valid_idxs(_lib.ptr(self.traj_end), self.size, _lib.ptr(rows), _lib.ptr(cnt),
+                                               stream), 'trl_valid_idxs')
+        return rows[: int(cnt.item())]
+
+    def _trl_batch(self, total, record, checked):
+        """A new TRL batch: the output dict in the reference's key order
+        (datasets.py:228-276), the descriptors of the fused columns (selectors
+        0..4), of the image columns selected through idx / next / goals and of
+        those selected through the midpoint, and the scalar outputs.  Each
+        distinct (source, selector) is gathered once; keys the reference
+        computes by the same expression share the tensor."""
+        torch = _torch()
+        ds = self.dataset
+        out, cols, vcols, mcols, made = {}, [], [], [], {}
+
+        def add(src_key, dst_key, select):
+            spec = self._visual_spec(src_key, dst_key)
+            dst = made.get((src_key, select, spec))
+            if dst is None:
+                if spec is not None:
+                    # the midpoint's image columns go to a gather of their own,
+                    # which reads value_midpoint_idxs as its idxs (selector 0)
+                    mid = select == TRL_SELECT_MIDPOINT
+                    dst, vc = self._vcolumn(src_key, 0 if mid else select, spec, total)
+                    (mcols if mid else vcols).append(vc)
+                else:
+                    src = ds[src_key]
+                    dst = torch.empty((total,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
+                    cols.append(self._column(src_key, dst, select))
+                made[(src_key, select, spec)] = dst
+            out[dst_key] = dst
+
+        def scalar(dtype):
+            return torch.empty(total, dtype=dtype, device=self.device)
+
+        i64, f64 = torch.int64, torch.float64
+        for k in ds.keys():
+            add(k, k, 0)
+        if 'next_observations' not in ds:
+            add('observations', 'next_observations', 1)
+        goal_src = 'oracle_reps' if 'oracle_reps' in ds else 'observations'
+        add(goal_src, 'value_goals', 2)
+        add(goal_src, 'actor_goals', 3)
+        out['masks'], out['rewards'] = scalar(f64), scalar(f64)
+        add('observations', 'value_goal_observations', 2)
+        add('observations', 'actor_goal_observations', 2)  # the value goal, as the reference (datasets.py:262)
+        out['value_offsets'], out['value_midpoint_offsets'] = scalar(i64), scalar(i64)
+        add('observations', 'value_midpoint_observations', TRL_SELECT_MIDPOINT)
+        add('actions', 'value_midpoint_actions', TRL_SELECT_MIDPOINT)
+        add('actions', 'next_actions', 1)
+        add(goal_src, 'value_midpoint_goals', TRL_SELECT_MIDPOINT)
+        add(goal_src, 'value_cur_goals', 0)
+        add(goal_src, 'value_next_goals', 1)
+        # index outputs only when something reads them (the gathers of a visual batch, a recording call)
+        idx_t = {'_' + k: scalar(i64) for k in (_TRL_SCALARS[:4] if (record or self._visual) else ())}
+        bad = torch.zeros(1, dtype=i64, device=self.device) if checked else None
+        outs = TrlOutputs(*[_lib.ptr(idx_t.get('_' + k)) for k in _TRL_SCALARS[:4]],
+                          *[out[k].data_ptr() for k in _TRL_SCALARS[4:8]], _lib.ptr(bad))
+        col_keep = (GcColumn * max(1, len(cols)))(*cols)
+        vcol_keep = (VisualColumn * max(1, len(vcols)))(*vcols)
+        mcol_keep = (VisualColumn * max(1, len(mcols)))(*mcols)
+        vidx = midx = None
+        if self._visual:
+            vidx = VisualIndices(idx_t['_idxs'].data_ptr(), idx_t['_value_goal_idxs'].data_ptr(),
+                                 idx_t['_actor_goal_idxs'].data_ptr(), None)
+            midx = VisualIndices(idx_t['_value_midpoint_idxs'].data_ptr(), None, None, None)
+        return (out, ctypes.cast(col_keep, ctypes.c_void_p), len(cols), outs,
+                ctypes.cast(vcol_keep, ctypes.c_void_p), len(vcols), vidx,
+                ctypes.cast(mcol_keep, ctypes.c_void_p), len(mcols), midx, idx_t, bad,
+                (col_keep, vcol_keep, mcol_keep))
+
+    def _sample_trl_call(self, batch_size, idxs=None, evaluation=False, draws=None, record_draws=False,
+                         num_batches=1, out=None):
+        """``sample`` of a TRL sampler (see ``sample`` for the arguments)."""
+        return self._sample_trl(int(batch_size), int(num_batches), idxs, evaluation, draws, record_draws, out)
+
+    def _sample_trl(self, B, nb, idxs, evaluation, draws, record_draws, out):
+        """sample() of a TRL sampler (datasets.py:213-294 with the branch of
+        254-276): one ``trl_sample_kernel`` launch (``ogbx_trl_sample``) over
+        the non-image columns; a visual sampler adds one ``ogbx_visual_gather``
+        over the image columns selected through idx / next / goals and one over
+        those selected through the midpoint (same seed and call, so the same
+        crop offsets).  ``draws`` also takes ``'midpoint'``, the rows the
+        reference's ``randint(idxs, value_goal_idxs)`` returned."""
+        torch = _torch()
+        total = B * nb
+        ds = self.dataset
+        if (ds is not self._tok_ds or getattr(ds, '_gen', None) != self._tok_gen
+                or (self._rec_src and tuple(map(_VERSION, self._rec_tensors)) != self._rec_versions)):
+            self._refresh_record()
+            self._trl_cache.clear()
+        # the coin of datasets.py:278-279, on the host; the offsets are device draws
+        crop = bool(self._visual and self._p_aug_live and not evaluation and np.random.rand() < self._p_aug)
+        draws = dict(draws or {})
+        crop_from = draws.pop('crop_from', None)
+        midpoint = draws.pop('midpoint', None)
+        cf = mid_in = None
+        if crop and crop_from is not None:
+            cf = _to_device(crop_from, self.device).to(torch.int64)
+            if tuple(cf.shape) != (total, 2):
+                raise ValueError(f"draws['crop_from'] must have shape ({total}, 2), got {tuple(cf.shape)}")
+        if midpoint is not None:
+            mid_in = _to_device(midpoint, self.device).to(torch.int64).reshape(-1)
+            if mid_in.numel() != total:
+                raise ValueError(f"draws['midpoint'] must have {total} entries, got {mid_in.numel()}")
+        # explicit idxs or injected draws may put a value goal at or before its
+        # sample: such a call has the kernel count those samples and reads the
+        # count back (one sync); Philox draws on the pick table cannot
+        checked = idxs is not None or bool(draws) or mid_in is not None
+        plain_call = not checked and crop_from is None and not record_draws
+        hit = self._trl_cache.get(id(out)) if (out is not None and plain_call) else None
+        if hit is not None and hit[0] is out and hit[1] == (B, nb):
+            st = hit[2]
+        else:
+            st = self._trl_batch(total, record_draws, checked)
+            if plain_call:
+                if len(self._trl_cache) >= 2:
+                    self._trl_cache.clear()
+                self._trl_cache[id(st[0])] = (st[0], (B, nb), st)
+        out, col_arr, ncols, outs, vcol_arr, nvcols, vidx, mcol_arr, nmcols, midx, idx_t, bad, _ = st
+        dr, staged, rec, rec_t = self._stage(total, idxs, draws, record_draws)
+        mid_rec = torch.empty(total, dtype=torch.int64, device=self.device) if record_draws else None
+        seed, call = self._next_seed()
+        stream = _lib.stream_of(self.device)
+        L = self._L
+        _lib.check(L.ogbx_trl_sample(self._buf, self._cfg, col_arr, ncols, B, nb, dr, _lib.ptr(mid_in), seed, call,
+                                     outs, rec, _lib.ptr(mid_rec), stream), 'trl_sample')
+        cf_out = None
+        if self._visual:
+            cf_out = torch.empty((total, 2), dtype=torch.int64, device=self.device) if (crop and record_draws) \
+                else None
+            F, draw = self._frame_stack or 1, int(crop and cf is None)
+            _lib.check(L.ogbx_visual_gather(self._buf, None, vcol_arr, nvcols, total, vidx, F, CROP_PADDING,
+                                            _lib.ptr(cf), draw, seed, call, _lib.ptr(cf_out), stream),
+                       'visual_gather')
+            # the crop draw is keyed by (sample, call) alone: the same offsets
+            _lib.check(L.ogbx_visual_gather(self._buf, None, mcol_arr, nmcols, total, midx, F, CROP_PADDING,
+                                            _lib.ptr(cf), draw, seed, call, None, stream), 'visual_gather')
+        elif self._p_aug_live and not evaluation:
+            np.random.rand()  # the coin; nothing of a non-visual batch is cropped
+        del staged, cf, mid_in  # alive until the launches were issued
+        if bad is not None:
+            n = int(bad.item())
+            if n:
+                raise ValueError(f'trl_sample: {n} of {total} samples have no row between the sample and its value '
+                                 f'goal (an index names the last row of its trajectory, or the injected draws put '
+                                 f'the value goal at or before the sample)')
+        if record_draws:
+            rec_t['midpoint'] = mid_rec
+            if cf_out is not None:
+                rec_t['crop_from'] = cf_out
+            out.update({'_draws': rec_t, **idx_t})
+        return out
+
     def _sample_new(self, B, nb, idxs, draws, record_draws, keys, plain_call, shape):
         """A call into a new batch: allocate it, stage idxs / draws, launch
         through the plan (plain call; the batch's slot is remembered for
@@ -949,6 +1203,7 @@ class HGCDataset(GCDataset):
                     'high_actor_goals', 'high_actor_actions', 'high_actor_next_observations', 'low_actor_goals',
                     'low_actor_goal_observations', 'low_actor_next_observations')
     _CROP_KEYS = tuple(k for k in _VISUAL_KEYS if k not in ('high_value_reps', 'low_value_goals'))
+    _TRL_OK = False
 
     def _hcfg_ptr(self):
         return ctypes.byref(self._hcfg)
