@@ -123,6 +123,7 @@ enum StreamTag : uint32_t {
   kTagPowderRand = 0x50570003u,
   kTagGcSample = 0x47430001u,
   kTagHgcSample = 0x47430002u,
+  kTagAtcSample = 0x41540001u,
 };
 
 inline void seed_key(uint64_t seed, uint32_t tag, uint32_t* k0, uint32_t* k1) {

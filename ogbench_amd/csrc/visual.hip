@@ -13,7 +13,8 @@
 // when they exceed the LDS budget) in LDS with the widest aligned loads, and
 // composes the output -- pixels of F * px_bytes bytes, shifted by the crop --
 // from LDS in 16-byte units aligned to the destination.  An unstacked,
-// uncropped column is a plain row copy and skips LDS.
+// uncropped column is a plain row copy and skips LDS.  The staging and the
+// compose are visual_tile.h's, shared with atc.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,11 +22,9 @@
 #include "../../include/ogbx_visual.h"
 #include "common.h"
 #include "gc_select.h"
+#include "visual_tile.h"
 
 namespace ogbx {
-
-constexpr int kVisThreads = 256;
-constexpr uint32_t kVisLdsMax = 64u * 1024u;  // dynamic LDS without an attribute call
 
 struct VisColumns {
   ogbx_visual_column c[OGBX_VISUAL_MAX_COLS];
@@ -46,29 +45,6 @@ struct VisArgs {
   int32_t num_cols;
   int64_t total;
 };
-
-__device__ inline int64_t clamp_row(int64_t r, int64_t R) { return r < 0 ? 0 : (r >= R ? R - 1 : r); }
-__device__ inline int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// Global -> LDS (or global) copy of len bytes by the whole workgroup: 16-byte
-// units when both sides allow it, else 4-byte units, the remainder in bytes.
-__device__ inline void copy_bytes(uint8_t* __restrict__ d, const uint8_t* __restrict__ g, int64_t len) {
-  const int t = threadIdx.x;
-  const uintptr_t a = (uintptr_t)g | (uintptr_t)d;
-  int64_t done = 0;
-  if ((a & 15) == 0) {
-    const int64_t n = len >> 4;
-    for (int64_t i = t; i < n; i += kVisThreads)
-      reinterpret_cast<uint4*>(d)[i] = reinterpret_cast<const uint4*>(g)[i];
-    done = n << 4;
-  } else if ((a & 3) == 0) {
-    const int64_t n = len >> 2;
-    for (int64_t i = t; i < n; i += kVisThreads)
-      reinterpret_cast<uint32_t*>(d)[i] = reinterpret_cast<const uint32_t*>(g)[i];
-    done = n << 2;
-  }
-  for (int64_t i = done + t; i < len; i += kVisThreads) d[i] = g[i];
-}
 
 // The row a column's selector picks for sample s (numbering of
 // ogbx_gc_column.select; every index clamped into the buffer).
@@ -109,16 +85,7 @@ __global__ void __launch_bounds__(kVisThreads) visual_gather_kernel(VisArgs a, V
 
   const int64_t r = select_row(a, col.select, s);
   const int F = col.stack ? a.frame_stack : 1;
-  // first row of r's trajectory among the F - 1 rows before r
-  int64_t start = r;
-  if (F > 1) {
-    const int64_t te = a.traj_end[r];
-    for (int k = 1; k < F; ++k) {
-      const int64_t cand = r - k;
-      if (cand < 0 || a.traj_end[cand] != te) break;
-      start = cand;
-    }
-  }
+  const int64_t start = stack_start(a.traj_end, r, F);
 
   const int p = a.padding;
   int cy = p, cx = p;  // identity
@@ -147,89 +114,10 @@ __global__ void __launch_bounds__(kVisThreads) visual_gather_kernel(VisArgs a, V
     }
   }
 
-  const int H = col.height, W = col.width, px = col.px_bytes;
-  const int rb = W * px;             // source row bytes
-  const int64_t fb = (int64_t)H * rb;  // source frame bytes
-  const int opx = F * px;            // output pixel bytes
-  const int orb = W * opx;           // output row bytes
-  const uint8_t* __restrict__ src = static_cast<const uint8_t*>(col.src);
-  uint8_t* __restrict__ dst = static_cast<uint8_t*>(col.dst) + s * ((int64_t)H * orb);
-
-  if (F == 1 && cy == p && cx == p) {  // a row copy
-    copy_bytes(dst, src + r * fb, fb);
-    return;
-  }
-
-  const int fstride = (int)((a.lds_bytes / (uint32_t)F) & ~15u);  // LDS bytes per staged frame
-  const int band = H < fstride / rb ? H : fstride / rb;            // output rows per pass (>= 1)
-  for (int y0 = 0; y0 < H; y0 += band) {
-    const int y1 = y0 + band < H ? y0 + band : H;
-    const int sy_lo = clampi(y0 + cy - p, H - 1), sy_hi = clampi(y1 - 1 + cy - p, H - 1);
-    const int len = (sy_hi - sy_lo + 1) * rb;  // <= band * rb <= fstride
-    if (y0 > 0) __syncthreads();               // the previous band was composed
-    for (int j = 0; j < F; ++j) {
-      int64_t row = r - (F - 1 - j);
-      row = row < start ? start : row;
-      copy_bytes(lds + j * fstride, src + row * fb + (int64_t)sy_lo * rb, len);
-    }
-    __syncthreads();
-
-    // compose rows [y0, y1) in 16-byte units aligned to the destination; the
-    // first and last unit may be partial (the neighbouring bytes belong to
-    // another band or another sample) and are stored bytewise
-    uint8_t* __restrict__ D = dst + (int64_t)y0 * orb;
-    const int L = (y1 - y0) * orb;
-    const int head = (int)((uintptr_t)D & 15);
-    const int nunits = (head + L + 15) >> 4;
-    for (int u = t; u < nunits; u += kVisThreads) {
-      const int o0 = u * 16 - head;
-      const int b0 = o0 < 0 ? -o0 : 0;
-      const int b1 = L - o0 < 16 ? L - o0 : 16;
-      const int o = o0 + b0;
-      int yy = o / orb;
-      const int rem = o - yy * orb;
-      int xx = rem / opx;
-      const int r2 = rem - xx * opx;
-      int jj = r2 / px;
-      int kk = r2 - jj * px;
-      int pix = (clampi(y0 + yy + cy - p, H - 1) - sy_lo) * rb + clampi(xx + cx - p, W - 1) * px;
-      uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        if (q >= b0 && q < b1) {
-          w[q >> 2] |= (uint32_t)lds[jj * fstride + pix + kk] << (8 * (q & 3));
-          if (++kk == px) {
-            kk = 0;
-            if (++jj == F) {
-              jj = 0;
-              if (++xx == W) {
-                xx = 0;
-                ++yy;
-              }
-              pix = (clampi(y0 + yy + cy - p, H - 1) - sy_lo) * rb + clampi(xx + cx - p, W - 1) * px;
-            }
-          }
-        }
-      }
-      if (b0 == 0 && b1 == 16) {
-        *reinterpret_cast<uint4*>(D + o0) = make_uint4(w[0], w[1], w[2], w[3]);
-      } else {
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          if (q >= b0 && q < b1) D[o0 + q] = (uint8_t)(w[q >> 2] >> (8 * (q & 3)));
-      }
-    }
-  }
-}
-
-// Device memory of `device`?
-static bool on_device(const void* ptr, int device) {
-  hipPointerAttribute_t attr{};
-  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return attr.type == hipMemoryTypeDevice && attr.device == device;
+  const int orb = col.width * (F * col.px_bytes);  // output row bytes
+  uint8_t* dst = static_cast<uint8_t*>(col.dst) + s * ((int64_t)col.height * orb);
+  compose_image(lds, a.lds_bytes, VisGeom{col.src, col.height, col.width, col.px_bytes}, r, start, F, cy, cx, p,
+                dst);
 }
 
 }  // namespace ogbx
@@ -274,8 +162,7 @@ ogbx_status ogbx_visual_gather(const ogbx_gc_buffer* buf, const ogbx_hgc_config*
     const int64_t F = c.stack ? frame_stack : 1;
     const int64_t row_bytes = (int64_t)c.width * c.px_bytes, frame = row_bytes * c.height;
     OGBX_CHECK(frame * F <= (1ll << 30), OGBX_EINVAL, who + "image too large");
-    const int64_t need = F * ((frame + 15) & ~15ll);
-    lds = std::max<uint32_t>(lds, (uint32_t)std::min<int64_t>(need, kVisLdsMax));
+    lds = std::max<uint32_t>(lds, vis_lds_bytes(frame, F));
     vc.c[i] = c;
   }
   for (int i = 0; i < num_cols; ++i) {  // at least one image row per staged frame

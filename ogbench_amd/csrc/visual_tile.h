@@ -1,0 +1,167 @@
+// visual_tile.h -- what the image kernels of visual.hip and atc.hip share: one
+// workgroup stages the F source frames of one selector row (or a band of their
+// rows when they exceed the LDS budget) in LDS with the widest aligned loads
+// and composes one output image -- pixels of F * px_bytes bytes, shifted by
+// the crop -- from LDS in 16-byte units aligned to the destination.  Internal
+// to libogbx.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ogbx {
+
+constexpr int kVisThreads = 256;
+constexpr uint32_t kVisLdsMax = 64u * 1024u;  // dynamic LDS without an attribute call
+
+// Geometry of one image column: the source holds UNSTACKED frames, dense
+// [R, height, width, px_bytes].
+struct VisGeom {
+  const void* src;
+  int32_t height, width;
+  int32_t px_bytes;  // bytes of one pixel of ONE frame
+};
+
+__device__ inline int64_t clamp_row(int64_t r, int64_t R) { return r < 0 ? 0 : (r >= R ? R - 1 : r); }
+__device__ inline int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// Global -> LDS (or global) copy of len bytes by the whole workgroup: 16-byte
+// units when both sides allow it, else 4-byte units, the remainder in bytes.
+__device__ inline void copy_bytes(uint8_t* __restrict__ d, const uint8_t* __restrict__ g, int64_t len) {
+  const int t = threadIdx.x;
+  const uintptr_t a = (uintptr_t)g | (uintptr_t)d;
+  int64_t done = 0;
+  if ((a & 15) == 0) {
+    const int64_t n = len >> 4;
+    for (int64_t i = t; i < n; i += kVisThreads)
+      reinterpret_cast<uint4*>(d)[i] = reinterpret_cast<const uint4*>(g)[i];
+    done = n << 4;
+  } else if ((a & 3) == 0) {
+    const int64_t n = len >> 2;
+    for (int64_t i = t; i < n; i += kVisThreads)
+      reinterpret_cast<uint32_t*>(d)[i] = reinterpret_cast<const uint32_t*>(g)[i];
+    done = n << 2;
+  }
+  for (int64_t i = done + t; i < len; i += kVisThreads) d[i] = g[i];
+}
+
+// First row of r's trajectory among the F - 1 rows before r (r inside the
+// buffer): row r-s belongs to r's trajectory iff r-s >= 0 and
+// traj_end[r-s] == traj_end[r].
+__device__ __forceinline__ int64_t stack_start(const int64_t* __restrict__ traj_end, int64_t r, int F) {
+  int64_t start = r;
+  if (F > 1) {
+    const int64_t te = traj_end[r];
+    for (int k = 1; k < F; ++k) {
+      const int64_t cand = r - k;
+      if (cand < 0 || traj_end[cand] != te) break;
+      start = cand;
+    }
+  }
+  return start;
+}
+
+// The output image of selector row r, by the whole workgroup of kVisThreads
+// threads: channel block j (0..F-1) is the frame at row
+// max(r - (F-1-j), start) with start = stack_start(traj_end, r, F); the window
+// starts at (cy, cx) of the image padded by p edge pixels ((p, p) is the
+// identity).  lds: lds_bytes of 16-byte aligned LDS with at least one image
+// row per staged frame ((lds_bytes / F) & ~15 >= width * px_bytes); dst: the
+// dense [height, width, F * px_bytes] destination.
+__device__ __forceinline__ void compose_image(uint8_t* lds, uint32_t lds_bytes, const VisGeom& g, int64_t r,
+                                              int64_t start, int F, int cy, int cx, int p,
+                                              uint8_t* __restrict__ dst) {
+  const int t = threadIdx.x;
+  const int H = g.height, W = g.width, px = g.px_bytes;
+  const int rb = W * px;               // source row bytes
+  const int64_t fb = (int64_t)H * rb;  // source frame bytes
+  const int opx = F * px;              // output pixel bytes
+  const int orb = W * opx;             // output row bytes
+  const uint8_t* __restrict__ src = static_cast<const uint8_t*>(g.src);
+
+  if (F == 1 && cy == p && cx == p) {  // a row copy
+    copy_bytes(dst, src + r * fb, fb);
+    return;
+  }
+
+  const int fstride = (int)((lds_bytes / (uint32_t)F) & ~15u);  // LDS bytes per staged frame
+  const int band = H < fstride / rb ? H : fstride / rb;         // output rows per pass (>= 1)
+  for (int y0 = 0; y0 < H; y0 += band) {
+    const int y1 = y0 + band < H ? y0 + band : H;
+    const int sy_lo = clampi(y0 + cy - p, H - 1), sy_hi = clampi(y1 - 1 + cy - p, H - 1);
+    const int len = (sy_hi - sy_lo + 1) * rb;  // <= band * rb <= fstride
+    if (y0 > 0) __syncthreads();               // the previous band was composed
+    for (int j = 0; j < F; ++j) {
+      int64_t row = r - (F - 1 - j);
+      row = row < start ? start : row;
+      copy_bytes(lds + j * fstride, src + row * fb + (int64_t)sy_lo * rb, len);
+    }
+    __syncthreads();
+
+    // compose rows [y0, y1) in 16-byte units aligned to the destination; the
+    // first and last unit may be partial (the neighbouring bytes belong to
+    // another band or another sample) and are stored bytewise
+    uint8_t* __restrict__ D = dst + (int64_t)y0 * orb;
+    const int L = (y1 - y0) * orb;
+    const int head = (int)((uintptr_t)D & 15);
+    const int nunits = (head + L + 15) >> 4;
+    for (int u = t; u < nunits; u += kVisThreads) {
+      const int o0 = u * 16 - head;
+      const int b0 = o0 < 0 ? -o0 : 0;
+      const int b1 = L - o0 < 16 ? L - o0 : 16;
+      const int o = o0 + b0;
+      int yy = o / orb;
+      const int rem = o - yy * orb;
+      int xx = rem / opx;
+      const int r2 = rem - xx * opx;
+      int jj = r2 / px;
+      int kk = r2 - jj * px;
+      int pix = (clampi(y0 + yy + cy - p, H - 1) - sy_lo) * rb + clampi(xx + cx - p, W - 1) * px;
+      uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        if (q >= b0 && q < b1) {
+          w[q >> 2] |= (uint32_t)lds[jj * fstride + pix + kk] << (8 * (q & 3));
+          if (++kk == px) {
+            kk = 0;
+            if (++jj == F) {
+              jj = 0;
+              if (++xx == W) {
+                xx = 0;
+                ++yy;
+              }
+              pix = (clampi(y0 + yy + cy - p, H - 1) - sy_lo) * rb + clampi(xx + cx - p, W - 1) * px;
+            }
+          }
+        }
+      }
+      if (b0 == 0 && b1 == 16) {
+        *reinterpret_cast<uint4*>(D + o0) = make_uint4(w[0], w[1], w[2], w[3]);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+          if (q >= b0 && q < b1) D[o0 + q] = (uint8_t)(w[q >> 2] >> (8 * (q & 3)));
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- host side
+// Device memory of `device`?
+static bool on_device(const void* ptr, int device) {
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return attr.type == hipMemoryTypeDevice && attr.device == device;
+}
+
+// Dynamic LDS for images of `frame` bytes stacked F deep: all F frames padded
+// to 16 bytes when they fit the budget, else the budget (the band loop).
+static uint32_t vis_lds_bytes(int64_t frame, int64_t F) {
+  const int64_t need = F * ((frame + 15) & ~15ll);
+  return (uint32_t)(need < (int64_t)kVisLdsMax ? need : (int64_t)kVisLdsMax);
+}
+
+}  // namespace ogbx

@@ -8,7 +8,12 @@ Batched, device-side counterparts of impls/utils/datasets.py (hliuson/ogbench):
   GCDataset  ~ GCDataset (datasets.py:149-366): ``sample(batch_size, idxs=None,
                evaluation=False)`` returns the same keys as the reference
                (every dataset key, ``next_observations``, ``value_goals``,
-               ``actor_goals``, ``masks``, ``rewards``).
+               ``actor_goals``, ``masks``, ``rewards``);
+  HGCDataset ~ HGCDataset (datasets.py:467-643);
+  ATCDataset ~ ATCDataset (datasets.py:369-464): ``sample(batch_size, k,
+               evaluation=False)`` returns ``observations`` and
+               ``positive_observations``, k rows apart in one trajectory, in
+               one launch of ``atc_sample_kernel`` (include/ogbx_atc.h).
 
 Every sample is ONE launch of ``gc_sample_kernel`` (libogbx): index draw,
 trajectory-end lookup, hindsight goal relabel and the row gathers of every
@@ -170,6 +175,25 @@ class TrlOutputs(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in _TRL_SCALARS]
 
 
+ATC_CROP_PADDING = 4  # ATCDataset.augment's default augment_padding (datasets.py:440)
+
+
+class AtcColumn(ctypes.Structure):
+    _fields_ = [
+        ('src', ctypes.c_void_p),
+        ('anchor', ctypes.c_void_p),
+        ('positive', ctypes.c_void_p),
+        ('height', ctypes.c_int32),
+        ('width', ctypes.c_int32),
+        ('px_bytes', ctypes.c_int32),
+        ('crop', ctypes.c_int32),
+    ]
+
+
+class AtcOutputs(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('idxs', 'pick', 'crop_from', 'bad_count')]
+
+
 def _bind():
     L = _lib.lib()
     if not getattr(L, '_gc_bound', False):
@@ -226,6 +250,18 @@ def _bind():
         L.ogbx_trl_valid_idxs.restype = ctypes.c_int32
         L.ogbx_trl_valid_idxs.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p]
+        # include/ogbx_atc.h (likewise)
+        L.ogbx_atc_api_version.restype = ctypes.c_int32
+        L.ogbx_atc_api_version.argtypes = []
+        L.ogbx_atc_valid_idxs.restype = ctypes.c_int32
+        L.ogbx_atc_valid_idxs.argtypes = [P(GcBuffer), ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p]
+        L.ogbx_atc_sample.restype = ctypes.c_int32
+        L.ogbx_atc_sample.argtypes = [
+            P(GcBuffer), P(AtcColumn), ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+            ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+            ctypes.c_uint64, ctypes.c_uint64, P(AtcOutputs), ctypes.c_void_p,
+        ]
         L._gc_bound = True
     return L
 
@@ -1312,3 +1348,244 @@ class HGCDataset(GCDataset):
     def _direct(self, col_arr, ncols, B, nb, dr, seed, call, outs, rec, stream):
         return self._Lh.ogbx_hgc_sample(self._buf, self._cfg, self._hcfg, col_arr, ncols, B, nb, dr, seed, call,
                                         outs, rec, stream)
+
+
+# ----------------------------------------------------------------------------- ATCDataset
+
+
+class ATCDataset:
+    """Anchor / positive observation pairs for ATC pretraining (reference:
+    datasets.py:369-464; consumed by impls/pretrain_atc.py:167-251).
+
+    config keys read (as the reference): frame_stack, p_aug, augment_padding
+    (default 4).  ``sample(batch_size, k)`` returns ``observations`` (rows
+    idx) and ``positive_observations`` (rows idx + k), idx drawn uniformly from
+    valid(k): the candidates c (``dataset.valid_idxs`` when the dataset has
+    'valids', else every row), in order, with c + k inside c's trajectory.
+    ONE launch of ``atc_sample_kernel`` (``ogbx_atc_sample``,
+    include/ogbx_atc.h) draws, stacks, crops and writes both keys.
+
+    With ``frame_stack = F`` both keys hold F frames stacked on the last axis,
+    channel block j the frame at row max(r - (F-1-j), first row of r's
+    trajectory); this needs a compact dataset (no 'next_observations').
+    ``preprocess_frame_stack`` is accepted and has no effect: the reference's
+    two settings give identical batches, and here the frames always stay
+    unstacked in HBM, so ``sampler.dataset['observations']`` stays unstacked.
+    With ``p_aug > 0`` a call whose coin comes up (one ``np.random.rand()``
+    per call, not under ``evaluation``; the rule of GCDataset) draws one
+    offset pair per sample on the device and crops both keys with it when the
+    observations are 4-D.
+
+    valid(k).  On a periodic layout (``periodic_layout``: equal trajectories,
+    the OGBench layout) a pick's row is a closed form of k and no table is
+    built.  Otherwise valid(k) is compacted on the device
+    (``ogbx_atc_valid_idxs``) once per k and kept in a cache of at most
+    ``TABLE_CACHE`` tables, the least recently used dropped: a training run
+    draws k from k_min..k_max on every step, and a table is 8 bytes per row.
+    An empty valid(k) raises the reference's ValueError, decided on the host
+    before any sample launch; k < 0 raises ValueError too (the reference would
+    wrap around the buffer).
+
+    ``draws`` takes ``'pick'`` (positions into valid(k)) and ``'crop_from'``
+    ([B, 2], used when the call crops); ``record_draws`` adds ``_idxs`` and
+    ``_draws`` (``pick``, and ``crop_from`` on a call whose coin came up).
+    Explicit ``idxs`` that leave their trajectory (or the buffer) raise
+    ValueError with their count, read back after the launch; the Philox path
+    reads nothing back.  ``out=`` refills a batch returned by an earlier plain
+    call with the same batch_size in place (stream ordered) and returns it; k
+    may differ between the calls.  Seeds and calls are counted as in
+    GCDataset.  ``sampler.dataset`` may be reassigned and its observations
+    replaced or modified in place; the trajectory layout (fixed at
+    construction, as the reference's ``__post_init__`` fixes its own) must
+    stay.
+    """
+
+    TABLE_CACHE = 16  # valid(k) tables kept (non-periodic layouts)
+
+    def __init__(self, dataset, config, preprocess_frame_stack=True, seed=None, _periodic=True):
+        torch = _torch()
+        if not isinstance(dataset, Dataset):
+            dataset = Dataset(dataset)
+        self.dataset = dataset
+        self.config = config
+        self.preprocess_frame_stack = preprocess_frame_stack
+        self.size = dataset.size
+        self.device = dataset.device
+        fs = config.get('frame_stack')
+        self._frame_stack = int(fs) if fs is not None else None
+        if fs is not None:
+            # only compact (observation-only) datasets (datasets.py:395-396)
+            assert 'next_observations' not in dataset
+            assert 1 <= self._frame_stack <= 8 and dataset['observations'].dim() >= 2
+        self._padding = int(config.get('augment_padding', ATC_CROP_PADDING))
+        if self._padding < 0:
+            raise ValueError(f'augment_padding must be >= 0, got {self._padding}')
+        self._p_aug = config.get('p_aug')
+        self._p_aug_live = self._p_aug is not None and float(self._p_aug) > 0.0  # GCDataset's coin rule
+        L = self._L = _bind()
+        stream = _lib.stream_of(self.device)
+        if 'terminals' in dataset:
+            self.terminal_locs = nonzero_positive(dataset['terminals'])
+        else:
+            self.terminal_locs = torch.tensor([self.size - 1], dtype=torch.int64, device=self.device)
+        assert self.terminal_locs.numel() > 0 and int(self.terminal_locs[-1]) == self.size - 1
+        self.initial_locs = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device),
+                                       self.terminal_locs[:-1] + 1])
+        self.traj_end = torch.empty(self.size, dtype=torch.int64, device=self.device)
+        _lib.check(L.ogbx_gc_traj_end(_lib.ptr(self.terminal_locs), self.terminal_locs.numel(), self.size,
+                                      _lib.ptr(self.traj_end), stream))
+        # the candidates (datasets.py:422-425)
+        valid = dataset.valid_idxs if 'valids' in dataset else None
+        self._cand = valid
+        self.period = (0, 0, 0)
+        if _periodic and (valid is None or valid.numel() > 0):
+            self.period = periodic_layout(self.size, valid, self.traj_end[valid] if valid is not None
+                                          else self.traj_end)
+        self._buf = GcBuffer(self.size, _lib.ptr(valid), valid.numel() if valid is not None else 0,
+                             self.traj_end.data_ptr(), None, None, *self.period)
+        self._tables = {}  # k -> (valid(k) or None, its size), least recently used first
+        self._seed = int(seed) if seed is not None else None
+        self._calls = 0
+        self._out_cache = {}
+        self._tok_ds, self._tok_gen = dataset, dataset._gen
+        self._obs = dataset['observations']
+
+    _next_seed = GCDataset._next_seed
+
+    # ---------------------------------------------------------------- valid(k)
+    def _valid_k(self, k):
+        """(valid(k) as a device tensor, or None on a periodic layout; its size)."""
+        P, pp, E = self.period
+        if P > 0:
+            return None, (self.size // P) * max(0, min(pp, E - k + 1))
+        hit = self._tables.pop(k, None)
+        if hit is None:
+            torch = _torch()
+            ncand = self._cand.numel() if self._cand is not None else self.size
+            rows = torch.empty(max(ncand, 1), dtype=torch.int64, device=self.device)
+            cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+            _lib.check(self._L.ogbx_atc_valid_idxs(self._buf, k, _lib.ptr(rows), _lib.ptr(cnt),
+                                                   _lib.stream_of(self.device)), 'atc_valid_idxs')
+            n = int(cnt.item())
+            # a copy of its own size: the slice would keep all candidates' bytes alive
+            hit = (rows[:n].clone() if n else None, n)
+            while len(self._tables) >= max(1, self.TABLE_CACHE):
+                del self._tables[next(iter(self._tables))]
+        self._tables[k] = hit  # most recently used last
+        return hit
+
+    # ------------------------------------------------------------------ batches
+    def _refresh(self):
+        """The dataset object or one of its columns was replaced: the prepared
+        batches hold the old observations' pointer."""
+        ds = self.dataset
+        if not isinstance(ds, Dataset):
+            ds = self.dataset = Dataset(ds)
+        obs = ds['observations']
+        if obs.shape != self._obs.shape or obs.dtype != self._obs.dtype or obs.device != self._obs.device:
+            raise ValueError("dataset column 'observations' changed shape, dtype or device after the sampler was "
+                             'built')
+        self._obs = obs
+        self._out_cache.clear()
+        self._tok_ds, self._tok_gen = ds, ds._gen
+
+    def _batch(self, B):
+        """A new batch: the output dict (the reference's key order) and its
+        column descriptor."""
+        torch = _torch()
+        src = self._obs
+        shape = tuple(src.shape[1:])
+        F = self._frame_stack or 1
+        oshape = (B,) + shape[:-1] + (shape[-1] * F,) if shape else (B,)
+        out = {k: torch.empty(oshape, dtype=src.dtype, device=self.device)
+               for k in ('observations', 'positive_observations')}
+        # an image is [H, W, C]; any other row is a 1-row image of its leading elements
+        if len(shape) == 3:
+            H, W = shape[0], shape[1]
+        else:
+            H, W = 1, int(np.prod(shape[:-1], dtype=np.int64))
+        px = (shape[-1] if shape else 1) * src.element_size()
+        col = AtcColumn(src.data_ptr(), out['observations'].data_ptr(), out['positive_observations'].data_ptr(),
+                        H, W, px, int(src.dim() == 4))
+        return out, col
+
+    def sample(self, batch_size, k, evaluation=False, idxs=None, draws=None, record_draws=False, out=None):
+        """ATCDataset.sample (datasets.py:401-415), one launch.
+
+        k: the temporal offset, an int >= 0.
+        idxs: explicit anchor rows (each with idx + k inside its trajectory).
+        draws: optional dict of injected reference draws: ``'pick'``, the
+        positions into valid(k) of np.random.choice (datasets.py:404), and
+        ``'crop_from'``, the [batch_size, 2] offsets of augment()'s randint
+        (datasets.py:442), used when the call's coin comes up.
+        record_draws: also return ``_idxs`` and the draws the kernel used
+        (``_draws``).
+        out: a batch returned by an earlier call with the same batch_size (and
+        no idxs / draws / record_draws): refilled in place, stream ordered,
+        and returned.
+        """
+        torch = _torch()
+        B, k = int(batch_size), operator.index(k)
+        if k < 0:
+            raise ValueError(f'k must be >= 0, got {k}')
+        ds = self.dataset
+        if ds is not self._tok_ds or getattr(ds, '_gen', None) != self._tok_gen:
+            self._refresh()
+        table, n = self._valid_k(k)
+        if n == 0:
+            raise ValueError(f'No valid ATC indices found for k={k}.')
+        # the coin stays on the host (datasets.py:411-412); the offsets are device draws
+        crop = bool(self._p_aug_live and not evaluation and np.random.rand() < self._p_aug)
+        draws = dict(draws or {})
+        crop_from, pick = draws.pop('crop_from', None), draws.pop('pick', None)
+        if draws:
+            raise ValueError(f'unknown draws {sorted(draws)}')
+        cf = pk = ix = None
+        if crop and crop_from is not None:
+            cf = _to_device(crop_from, self.device).to(torch.int64)
+            if tuple(cf.shape) != (B, 2):
+                raise ValueError(f"draws['crop_from'] must have shape ({B}, 2), got {tuple(cf.shape)}")
+        if pick is not None:
+            pk = _to_device(pick, self.device).to(torch.int64).reshape(-1)
+            if pk.numel() != B:
+                raise ValueError(f"draws['pick'] must have {B} entries, got {pk.numel()}")
+        if idxs is not None:
+            ix = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
+            if ix.numel() != B:
+                raise ValueError(f'idxs must have {B} entries, got {ix.numel()}')
+        plain_call = ix is None and pk is None and crop_from is None and not record_draws
+        hit = self._out_cache.get(id(out)) if (out is not None and plain_call) else None
+        if hit is not None and hit[0] is out and hit[1] == B:
+            col = hit[2]
+        else:
+            out, col = self._batch(B)
+            if plain_call:
+                if len(self._out_cache) >= 2:
+                    self._out_cache.clear()
+                self._out_cache[id(out)] = (out, B, col)
+        rec = {}
+        if record_draws:
+            rec = dict(idxs=torch.empty(B, dtype=torch.int64, device=self.device),
+                       pick=torch.empty(B, dtype=torch.int64, device=self.device))
+            if crop:
+                rec['crop_from'] = torch.empty((B, 2), dtype=torch.int64, device=self.device)
+        # explicit rows may leave their trajectory: such a call has the kernel
+        # count them and reads the count back (one sync); picks cannot
+        bad = torch.zeros(1, dtype=torch.int64, device=self.device) if ix is not None else None
+        outs = AtcOutputs(_lib.ptr(rec.get('idxs')), _lib.ptr(rec.get('pick')), _lib.ptr(rec.get('crop_from')),
+                          _lib.ptr(bad))
+        seed, call = self._next_seed()
+        _lib.check(self._L.ogbx_atc_sample(
+            self._buf, col, B, k, _lib.ptr(table), n, self._frame_stack or 1, self._padding, _lib.ptr(ix),
+            _lib.ptr(pk), _lib.ptr(cf), int(crop and cf is None), seed, call, outs,
+            _lib.stream_of(self.device)), 'atc_sample')
+        del cf, pk  # alive until the launch was issued
+        if bad is not None:
+            nbad = int(bad.item())
+            if nbad:
+                raise ValueError(f'atc_sample: {nbad} of {B} samples have idx + k (k={k}) past the end of their '
+                                 f'trajectory, or idx outside the dataset')
+        if record_draws:
+            out['_idxs'] = rec.pop('idxs')
+            out['_draws'] = rec
+        return out
