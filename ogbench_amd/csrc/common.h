@@ -124,6 +124,7 @@ enum StreamTag : uint32_t {
   kTagGcSample = 0x47430001u,
   kTagHgcSample = 0x47430002u,
   kTagAtcSample = 0x41540001u,
+  kTagPlayPlan = 0x504C0001u,
 };
 
 inline void seed_key(uint64_t seed, uint32_t tag, uint32_t* k0, uint32_t* k1) {

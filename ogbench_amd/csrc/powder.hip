@@ -36,7 +36,9 @@
 #include <string>
 #include <vector>
 
+#include "../../include/ogbx_play.h"
 #include "common.h"
+#include "powder_play.h"
 #include "powder_schedule.h"
 
 namespace ogbx {
@@ -1039,6 +1041,57 @@ __global__ void __launch_bounds__(pwf_nt<WS>()) __attribute__((amdgpu_waves_per_
   if (rgb) fw.observe(rgb + (size_t)e * C * 3, 0, 0u, 0, 0, true);
 }
 
+// Data-collection reset (powderworld_env.py:284-352 with _mode ==
+// 'data_collection', include/ogbx_play.h): the blank walled world, no task, no
+// goal replay and no initial action, so no draw.  ctrl keeps task 1, a valid
+// index for the step kernels, whose tolerances are 0 on a data-mode handle.
+template <int WS>
+__global__ void __launch_bounds__(256) pw_data_reset_kernel(const PowderParams* __restrict__ Pp, PowderState S,
+                                                            const uint8_t* __restrict__ mask,
+                                                            uint8_t* __restrict__ obs) {
+  using G = Geo<WS>;
+  __shared__ PwShared<WS> sh;
+  const int64_t e = blockIdx.x;
+  if (mask != nullptr && mask[e] == 0) return;
+  Blk<WS> b(sh);
+  load_tables(sh, Pp);
+  __syncthreads();  // tables
+  const typename Blk<WS>::S own = b.reset_world(0, -1000, -1000, Pp->brush);
+  store_seg(S.world + (size_t)e * G::CELLS + b.r * G::W + b.c0, own);
+  b.observe(own, obs + (size_t)e * G::OBS, 0, 0u, 0, Pp->brush);
+  if (threadIdx.x == 0) {
+    S.ctrl[e] = 1 << 16;
+    S.elapsed[e] = 0;
+    S.episode[e] += 1u;
+  }
+}
+
+// Medium/hard: also zero momentum, velocity and goal ids, and a fresh render cache.
+template <int WS>
+__global__ void __launch_bounds__(pwf_nt<WS>()) __attribute__((amdgpu_waves_per_eu(kPwfWaves)))
+pwf_data_reset_kernel(const PowderParams* __restrict__ Pp, PowderState S, const uint8_t* __restrict__ mask,
+                      uint8_t* __restrict__ obs) {
+  constexpr int C = WS * WS;
+  __shared__ PwFullShared<WS> sh;
+  const int64_t e = blockIdx.x;
+  if (mask != nullptr && mask[e] == 0) return;
+  FW<WS> fw(sh);
+#ifdef OGBX_PWF_RULE_STAMPS
+  fw.diag_env = e;
+#endif
+  pwf_tables(sh, Pp);
+  fw.blank();
+#pragma unroll
+  for (int k = 0; k < FW<WS>::CPT; ++k) S.goal_env[(size_t)e * C + fw.cell(k)] = 0;
+  fw.store(S.world + (size_t)e * C, S.mom + (size_t)e * C, S.vel + (size_t)e * C);
+  fw.observe(obs + (size_t)e * C * 6, 0, 0u, 0, Pp->brush, false, S.crg + (size_t)e * C, S.cb + (size_t)e * C);
+  if (threadIdx.x == 0) {
+    S.ctrl[e] = 1 << 16;
+    S.elapsed[e] = 0;
+    S.episode[e] += 1u;
+  }
+}
+
 // Host-side task tables (powderworld_env.py:88-149), elem indices into
 // _elem_names = ['plant', 'stone'].
 static void easy_tasks(std::vector<std::vector<std::array<int, 3>>>& tasks) {
@@ -1208,6 +1261,7 @@ struct ogbx_powder_env {
   int32_t device = 0;
   int64_t n = 0;
   bool full = false;  // medium / hard element sets (full rule set)
+  bool data = false;  // data-collection mode (include/ogbx_play.h): no task, tolerances 0
   int32_t max_seq = 0;
   ogbx::PowderParams P;
   ogbx::PowderParams* Pd = nullptr;
@@ -1246,6 +1300,23 @@ constexpr auto pwf_step_kernel_sparse = pwf_step_kernel<WS, true>;
 template <int WS>
 constexpr int pw_nt() { return 256; }  // easy worlds and the light kernel
 }  // namespace
+
+ogbx_status ogbx::powder_data_reset(ogbx_powder_t e, const uint8_t* mask, uint8_t* obs, uint64_t seed, void* stream) {
+  OGBX_CHECK(e->data, OGBX_EINVAL,
+             "ogbx_play_powder_reset: the handle is in task mode (create it with pad = OGBX_POWDER_MODE_DATA)");
+  OGBX_HIP(hipSetDevice(e->device));
+  e->seed = seed;
+  if (e->full) {
+    PW_LAUNCH(pwf_data_reset_kernel, pwf_nt, e, (uint32_t)e->n, stream, e->Pd, e->S, mask, obs);
+    OGBX_LAUNCHED("pwf_data_reset_kernel");
+  } else {
+    PW_LAUNCH(pw_data_reset_kernel, pw_nt, e, (uint32_t)e->n, stream, e->Pd, e->S, mask, obs);
+    OGBX_LAUNCHED("pw_data_reset_kernel");
+  }
+  e->was_reset = true;
+  pwf_schedule_reset(e->sched, mask == nullptr);
+  return OGBX_OK;
+}
 
 extern "C" {
 
@@ -1287,12 +1358,15 @@ ogbx_status ogbx_powder_create(const ogbx_powder_opts* opts, int64_t n_envs, int
              "only the registered grid_size=4 / brush_size=4 are supported");
   OGBX_CHECK(opts->max_episode_steps > 0, OGBX_EINVAL, "max_episode_steps must be positive");
   OGBX_CHECK(opts->env_base >= 0, OGBX_EINVAL, "env_base must be >= 0");
+  OGBX_CHECK(opts->pad == 0 || opts->pad == OGBX_POWDER_MODE_DATA, OGBX_EINVAL,
+             "ogbx_powder_opts.pad must be 0 (task mode) or OGBX_POWDER_MODE_DATA");
   ogbx_status st = use_device(device);
   if (st != OGBX_OK) return st;
   auto* e = new ogbx_powder_env();
   e->device = device;
   e->n = n_envs;
   e->full = ne != 2;
+  e->data = opts->pad == OGBX_POWDER_MODE_DATA;
   PowderParams& P = e->P;
   std::memset(&P, 0, sizeof(P));
   P.H = P.W = ws;
@@ -1323,6 +1397,8 @@ ogbx_status ogbx_powder_create(const ogbx_powder_opts* opts, int64_t n_envs, int
   std::vector<PwSeq> tasks;
   std::vector<int> tols;
   task_tables(ne, tasks, tols);
+  // data mode: an error count (>= 0) is never below 0, so no step reports success
+  if (e->data) tols.assign(tols.size(), 0);
   P.num_tasks = (int)tasks.size();
   P.tol = tols[0];
   for (int t = 0; t < P.num_tasks; ++t) {
@@ -1420,6 +1496,7 @@ ogbx_status ogbx_powder_reset(ogbx_powder_t e, const int32_t* task_id, const uin
   OGBX_CHECK(rand == nullptr || e->full, OGBX_EINVAL, "rand fields apply to medium/hard worlds only");
   OGBX_CHECK(rand == nullptr || (task_id != nullptr && reset_action != nullptr && rand_rows >= e->max_seq + 1),
              OGBX_EINVAL, "injected rand needs task_id, reset_action and rand_rows >= longest task + 1");
+  OGBX_CHECK(!e->data, OGBX_EINVAL, "a data-collection handle has no task: reset it with ogbx_play_powder_reset");
   OGBX_HIP(hipSetDevice(e->device));
   e->seed = seed;
   uint32_t k0, k1, r0, r1;
@@ -1448,6 +1525,7 @@ ogbx_status ogbx_powder_step(ogbx_powder_t e, const int32_t* action, int32_t k_s
   OGBX_CHECK(e->was_reset, OGBX_ESTATE, "Cannot call env.step() before calling env.reset()");
   OGBX_CHECK(k_steps >= 1, OGBX_EINVAL, "k_steps must be >= 1");
   OGBX_CHECK(rand == nullptr || e->full, OGBX_EINVAL, "rand fields apply to medium/hard worlds only");
+  OGBX_CHECK(!(e->data && auto_reset), OGBX_EINVAL, "a data-collection handle does not auto-reset");
   OGBX_HIP(hipSetDevice(e->device));
   uint32_t k0, k1, a0, a1, r0, r1;
   seed_key(e->seed, kTagPowderReset, &k0, &k1);

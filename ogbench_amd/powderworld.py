@@ -1,10 +1,13 @@
 """Batched powderworld environments on MI355X.
 
 ``PowderworldEnv`` is the batched counterpart of the reference
-``PowderworldEnv`` (ogbench/powderworld/powderworld_env.py:21-476) in 'task'
-mode under gymnasium's TimeLimit (registry: ogbench/powderworld/__init__.py):
-the same constructor options, Discrete action protocol (element, x, y over
-three steps), task table, goal observation and tolerance-based success.  Every
+``PowderworldEnv`` (ogbench/powderworld/powderworld_env.py:21-476) under
+gymnasium's TimeLimit (registry: ogbench/powderworld/__init__.py): the same
+constructor options, Discrete action protocol (element, x, y over three
+steps), task table, goal observation and tolerance-based success in 'task'
+mode; in 'data_collection' mode (include/ogbx_play.h) resets give the empty
+walled world, there is no task or goal, reward is 0, nothing terminates and
+``info`` is ``{}`` (``datagen.collect_powderworld`` drives it).  Every
 env's world lives in HBM; a step is one ``ogbx_powder_step`` launch in which
 each env's 256-thread workgroup runs the cellular automaton in LDS.
 
@@ -30,7 +33,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _play
 from .locomaze import _from_ptr, _resolve_device, _torch, _zero_episodes
 from .powder_tasks import task_names, task_sequences, task_tols
 from .spaces import Box, Discrete
@@ -58,9 +61,10 @@ class PowderworldEnv:
         seed=None,
         env_base=0,
     ):
-        assert mode in ('task', 'data'), 'mode must be task or data'
-        if mode != 'task':
-            raise NotImplementedError("only mode='task' is implemented (data collection runs on the host)")
+        assert mode in ('task', 'data', 'data_collection'), 'mode must be task or data_collection'
+        mode = 'data_collection' if mode == 'data' else mode  # 'data': the earlier spelling
+        if mode != 'task' and auto_reset:
+            raise ValueError('auto_reset is a task-mode option: data collection runs lock-step rounds')
         if num_elems not in ELEM_NAMES:
             raise ValueError(f'num_elems must be one of {sorted(ELEM_NAMES)}')
         torch = _torch()
@@ -81,10 +85,11 @@ class PowderworldEnv:
             brush_size=self._brush_size,
             num_elems=self._num_elems,
             max_episode_steps=self.max_episode_steps,
+            pad=0 if mode == 'task' else _play.POWDER_MODE_DATA,
             env_base=int(env_base),
         )
         self.env_base = int(env_base)
-        L = _lib.lib()
+        L = _play.bind()
         h = _lib.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(L.ogbx_powder_create(opts, self.num_envs, self.device.index, h))
@@ -117,6 +122,8 @@ class PowderworldEnv:
         self._succ = torch.zeros(n, dtype=torch.uint8, **kw)
         self._seed = None
         self._init_seed = seed
+        self._sample_calls = 0
+        self._succ_k = None
         self.cur_task_id = None
 
     # ------------------------------------------------------------ lifecycle
@@ -317,17 +324,13 @@ class PowderworldEnv:
         """
         torch = _torch()
         options = {} if options is None else options
+        if self._mode != 'task':
+            return self._reset_data(seed, options, mask)
         if options.get('render_goal'):
             raise NotImplementedError('render_goal (PIL upscaling) is out of scope; use info["goal"]')
         if 'task_info' in options:
             raise NotImplementedError('custom task_info action sequences are not supported on the device')
-        if seed is not None:
-            # gymnasium reseeding: the Philox stream of every reset env restarts
-            self._seed = int(seed) & ((1 << 64) - 1)
-            _zero_episodes(self._scalar_view('episode'), mask, self.device)
-        elif self._seed is None:
-            self._seed = (int(self._init_seed) if self._init_seed is not None
-                          else int(np.random.randint(0, 2**63 - 1)))
+        self._reseed(seed, mask)
         task_t = None
         if 'task_id' in options:
             tid = options['task_id']
@@ -362,6 +365,52 @@ class PowderworldEnv:
         )
         return self._obs, {'goal': self._goal}
 
+    def _reseed(self, seed, mask):
+        if seed is not None:
+            # gymnasium reseeding: the Philox stream of every reset env restarts
+            self._seed = int(seed) & ((1 << 64) - 1)
+            _zero_episodes(self._scalar_view('episode'), mask, self.device)
+        elif self._seed is None:
+            self._seed = (int(self._init_seed) if self._init_seed is not None
+                          else int(np.random.randint(0, 2**63 - 1)))
+
+    def _reset_data(self, seed, options, mask):
+        """reset in data-collection mode (powderworld_env.py:284-352 without the
+        'task' branches): the empty walled world, stage 0, no task, no goal and
+        no initial action.  Returns (obs, {})."""
+        torch = _torch()
+        if options:
+            raise ValueError(f'data-collection resets take no options (got {sorted(options)}): there is no task')
+        self._reseed(seed, mask)
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask).to(self.device, torch.uint8).contiguous()
+        _lib.check(self._L.ogbx_play_powder_reset(self._h, _lib.ptr(m), _lib.ptr(self._obs), self._seed,
+                                                  self._stream()), 'reset')
+        return self._obs, {}
+
+    def sample_semantic_action(self):
+        """Batched sample_semantic_action (powderworld_env.py:446-451): int32
+        [N, 3] of (elem index, x, y), from the plan's Philox stream
+        (include/ogbx_play.h); a new draw per call."""
+        torch = _torch()
+        if self._seed is None:
+            self._reseed(None, None)
+        out = torch.empty(self.num_envs, 3, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.ogbx_play_sample_semantic(self._num_elems, self._xy_action_size, self.num_envs,
+                                                         self.env_base, self._seed, self._sample_calls,
+                                                         _lib.ptr(out), self._stream()), 'sample_semantic_action')
+        self._sample_calls += 1
+        return out
+
+    def sample_action(self):
+        """Batched sample_action (powderworld_env.py:439-444): int32 [N], a
+        valid action of every env's current stage."""
+        sem = self.sample_semantic_action()
+        stage = (self._scalar_view('ctrl') & 3).clamp(max=2).long()
+        return sem.gather(1, stage[:, None])[:, 0].contiguous()
+
     def _actions(self, action, shape):
         torch = _torch()
         if not isinstance(action, torch.Tensor):
@@ -390,7 +439,7 @@ class PowderworldEnv:
             'step',
         )
         torch = _torch()
-        info = {'success': self._succ.view(torch.bool)}
+        info = {'success': self._succ.view(torch.bool)} if self._mode == 'task' else {}
         return self._obs, self._reward, self._term.view(torch.bool), self._trunc.view(torch.bool), info
 
     def rollout(self, actions, draws=None, out=None, rand=None):
@@ -410,10 +459,17 @@ class PowderworldEnv:
                 truncated=torch.empty(K, self.num_envs, dtype=torch.uint8, **kw),
                 success=torch.empty(K, self.num_envs, dtype=torch.uint8, **kw),
             )
+            if self._mode != 'task':
+                del out['success']  # data collection computes no success
+        succ = out.get('success')
+        if succ is None:  # the C-ABI still wants somewhere to write its zeros
+            if self._succ_k is None or self._succ_k.shape[0] < K:
+                self._succ_k = torch.empty(K, self.num_envs, dtype=torch.uint8, device=self.device)
+            succ = self._succ_k
         _lib.check(
             self._L.ogbx_powder_step(self._h, _lib.ptr(a), K, _lib.ptr(d), _lib.ptr(r), _lib.ptr(out['obs']),
                                      _lib.ptr(out['reward']), _lib.ptr(out['terminated']),
-                                     _lib.ptr(out['truncated']), _lib.ptr(out['success']), int(self.auto_reset),
+                                     _lib.ptr(out['truncated']), _lib.ptr(succ), int(self.auto_reset),
                                      self._stream()),
             'rollout',
         )
