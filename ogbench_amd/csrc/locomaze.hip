@@ -21,9 +21,11 @@
 #include <cstring>
 #include <deque>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
+#include "goal_threshold.h"
 #include "point_physics.h"
 #include "point_contact.h"
 
@@ -55,6 +57,20 @@ struct MazeState {
   uint32_t* episode;
 };
 
+// What a step launch reads of MazeParams per wave, by value in the kernel
+// arguments: it arrives with the kernel's first scalar load clause instead of
+// by dependent scalar round trips through *Pp.  Filled once at create (every
+// field is fixed for the handle's lifetime); the tables indexed per lane
+// (tasks, teleports) stay behind Pp.
+struct MazeStepConsts {
+  const uint16_t* nbmask;  // &Pd->nbmask[0]
+  int64_t env_base;
+  double goal_tol;
+  double goal_s2max;  // goal_s2max(goal_tol): dist <= goal_tol  <=>  dist^2 <= goal_s2max
+  int32_t H, W, max_steps, n_tp_in;
+  int32_t success_pre, terminate_at_goal, reward_task_id, add_noise_to_goal;
+};
+
 }  // namespace ogbx
 
 struct ogbx_maze_env {
@@ -63,6 +79,7 @@ struct ogbx_maze_env {
   ogbx::MazeParams P;
   ogbx::MazeState S{};
   ogbx::MazeParams* Pd = nullptr;  // device copy of P (tables indexed per lane)
+  ogbx::MazeStepConsts C{};        // the step kernels' by-value part of P
   int16_t* bfs = nullptr;  // [H*W goal cell][H*W cell] BFS distances (maze.py:517-536)
   uint64_t seed = 0;
   bool was_reset = false;
@@ -103,7 +120,6 @@ __device__ inline void stage_nbmask(const MazeParams& P, uint16_t* nb_s) {
 // the table's address (no dependent read of H*W), issued together with the
 // env's state and action loads so that the whole prologue is one HBM round
 // trip; nbmask_commit stores it into LDS after them.
-constexpr int kStepBlock = 256;
 static_assert(kMaxCells == kStepBlock, "one wall-mask entry per thread of a step block");
 
 __device__ __forceinline__ uint16_t nbmask_fetch(const MazeParams* Pp) { return Pp->nbmask[threadIdx.x]; }
@@ -118,6 +134,14 @@ __device__ __forceinline__ void nbmask_commit(uint16_t* nb_s, uint16_t v) {
 __device__ inline bool goal_reached(double x, double y, double gx, double gy, double tol) {
   double dx = x - gx, dy = y - gy;
   return sqrt(fma(dy, dy, dx * dx)) <= tol;
+}
+
+// goal_reached(.., tol) with s2max = goal_s2max(tol) (goal_threshold.h): the
+// same squared distance compared before the square root, exactly the same
+// answer for every input (a NaN fails both).
+__device__ inline bool goal_within(double x, double y, double gx, double gy, double s2max) {
+  double dx = x - gx, dy = y - gy;
+  return fma(dy, dy, dx * dx) <= s2max;
 }
 
 // The four uniform(-1, 1) reset draws of one env, in reference order
@@ -138,33 +162,49 @@ __device__ inline int32_t draw_task(const MazeParams& P, uint64_t i, uint32_t ep
   return 1 + (int32_t)bounded_u32(c.x, (uint32_t)P.num_tasks);
 }
 
+// Cell centres (init x, init y, goal x, goal y) of a task row (init_i, init_j,
+// goal_i, goal_j): ij_to_xy, maze.py:558-562.
+__device__ inline void task_centres(const PointModel& pm, const int32_t* t, double c[4]) {
+  c[0] = t[1] * pm.unit - pm.off_x;
+  c[1] = t[0] * pm.unit - pm.off_y;
+  c[2] = t[3] * pm.unit - pm.off_x;
+  c[3] = t[2] * pm.unit - pm.off_y;
+}
+
+__device__ inline void reset_noise(const PointModel& pm, const double c[4], int32_t add_noise_to_goal,
+                                   const double r[4], double& x, double& y, double& gx, double& gy) {
+  x = c[0] + r[0] * pm.unit / 4.0;
+  y = c[1] + r[1] * pm.unit / 4.0;
+  if (add_noise_to_goal) {
+    gx = c[2] + r[2] * pm.unit / 4.0;
+    gy = c[3] + r[3] * pm.unit / 4.0;
+  } else {
+    gx = c[2];
+    gy = c[3];
+  }
+}
+
 // MazeEnv.reset for one env: returns init (x, y) and goal (gx, gy).
 // add_noise: xy + uniform(-1,1) * maze_unit / 4 (maze.py:564-567).
 __device__ inline void reset_one(const MazeParams& P, int32_t task, const double* task_xy,
                                  const double r[4], double& x, double& y, double& gx,
                                  double& gy) {
-  double ix, iy, bx, by;
+  double c[4];
   if (task_xy != nullptr) {
-    ix = task_xy[0];
-    iy = task_xy[1];
-    bx = task_xy[2];
-    by = task_xy[3];
+    for (int k = 0; k < 4; ++k) c[k] = task_xy[k];
   } else {
-    const int32_t* t = P.tasks[task - 1];
-    ix = t[1] * P.pm.unit - P.pm.off_x;
-    iy = t[0] * P.pm.unit - P.pm.off_y;
-    bx = t[3] * P.pm.unit - P.pm.off_x;
-    by = t[2] * P.pm.unit - P.pm.off_y;
+    task_centres(P.pm, P.tasks[task - 1], c);
   }
-  x = ix + r[0] * P.pm.unit / 4.0;
-  y = iy + r[1] * P.pm.unit / 4.0;
-  if (P.add_noise_to_goal) {
-    gx = bx + r[2] * P.pm.unit / 4.0;
-    gy = by + r[3] * P.pm.unit / 4.0;
-  } else {
-    gx = bx;
-    gy = by;
-  }
+  reset_noise(P.pm, c, P.add_noise_to_goal, r, x, y, gx, gy);
+}
+
+// reset_one from the task table with the model and the noise flag passed in:
+// the step kernels hold both without reading *Pp.
+__device__ inline void reset_from_task(const PointModel& pm, const int32_t* t, int32_t add_noise_to_goal,
+                                       const double r[4], double& x, double& y, double& gx, double& gy) {
+  double c[4];
+  task_centres(pm, t, c);
+  reset_noise(pm, c, add_noise_to_goal, r, x, y, gx, gy);
 }
 
 // ------------------------------------------------------------------ kernels
@@ -184,7 +224,7 @@ constexpr int kEpwReplicate = 0x100;
 __device__ inline int64_t env_of_lane(int epw, bool* writer) {
   const int lane = threadIdx.x & 63;
   const int e = epw & 0xFF;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t wave = ((int64_t)blockIdx.x * kStepBlock + threadIdx.x) >> 6;
   *writer = lane < e;
   if (lane >= e && !(epw & kEpwReplicate)) return -1;
   return wave * e + (lane & (e - 1));
@@ -248,54 +288,102 @@ __device__ unsigned long long g_wave_stamps[4096 * 4];
 
 typedef double f64x2 __attribute__((ext_vector_type(2)));  // 16-byte non-temporal stores
 
-template <bool kF64, bool kUntilDone>
+// Element i of a per-env array.  k32 (the plain step, n <= kPlainMaxEnvs): the
+// byte offset fits 32 bits, so the address is the scalar base plus one 32-bit
+// lane offset instead of a 64-bit multiply-add per array.
+constexpr int64_t kPlainMaxEnvs = (int64_t)1 << 27;  // 16-byte rows: offsets below 2^31
+
+template <bool k32, class T>
+__device__ __forceinline__ T* env_elem(T* base, int64_t i) {
+  if constexpr (k32) {
+    using B = std::conditional_t<std::is_const_v<T>, const char, char>;
+    return reinterpret_cast<T*>(reinterpret_cast<B*>(base) + (uint32_t)i * (uint32_t)sizeof(T));
+  } else {
+    return base + i;
+  }
+}
+
+// kPlain: the single env.step launch (maze_step_launch picks it for k_steps ==
+// 1, 64 envs per wave, no teleports, n <= kPlainMaxEnvs): k_steps, epw and the
+// teleport count are compile-time constants here, so the k loop, the teleport
+// block and the copy-lane logic fold away and with them the scalar registers
+// they held across the physics.  The step itself is the same code.
+template <bool kF64, bool kUntilDone, bool kPlain = false>
 __global__ void __launch_bounds__(256) maze_step_kernel(
-    const MazeParams* __restrict__ Pp, MazeState S, int64_t n, const void* __restrict__ action_v,
-    int32_t k_steps,
-    double* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ terminated,
-    uint8_t* __restrict__ truncated, uint8_t* __restrict__ success,
-    double* __restrict__ final_obs, int32_t auto_reset, uint32_t k0, uint32_t k1, int epw,
-    int32_t* __restrict__ steps_taken) {
+    const MazeStepConsts C, MazeState S, const void* __restrict__ action_v, int64_t n,  // read before the physics
+    double* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ terminated,  // and after it
+    uint8_t* __restrict__ truncated, uint8_t* __restrict__ success, int32_t auto_reset, int32_t k_steps_arg,
+    double* __restrict__ final_obs, uint32_t k0, uint32_t k1, int epw,
+    const MazeParams* __restrict__ Pp, int32_t* __restrict__ steps_taken) {
+  static_assert(!(kPlain && kUntilDone), "the plain instantiation is the single auto-reset step");
   const MazeParams& P = *Pp;
   OGBX_POINT_MODEL(pm, P);
+  const int32_t k_steps = kPlain ? 1 : k_steps_arg;
+  const int32_t n_tp_in = kPlain ? 0 : C.n_tp_in;
   __shared__ uint16_t nb_s[kMaxCells];
 #ifdef OGBX_WAVE_STAMPS
   const unsigned long long ws_t0 = wall_clock64(), ws_c0 = clock64();
 #endif
-  bool writer;
-  const int64_t i = env_of_lane(epw, &writer);
-  const bool live = i >= 0 && i < n;
-  // one HBM round trip before the first barrier: the wall-mask entry, the
-  // env's state and its first action
-  const uint16_t nbv = nbmask_fetch(Pp);
+#ifdef OGBX_STAGE_STAMPS
+  const unsigned long long ps_t0 = __builtin_amdgcn_s_memtime();
+  __builtin_amdgcn_sched_barrier(0);
+#endif
+  bool writer = true;
+  int64_t i;
+  bool live;
+  if constexpr (kPlain) {
+    const uint32_t t = blockIdx.x * kStepBlock + threadIdx.x;
+    i = t;
+    live = t < (uint32_t)n;
+  } else {
+    i = env_of_lane(epw, &writer);
+    live = i >= 0 && i < n;
+  }
+  // The constants the step reads before the physics, asked for here: the
+  // compiler otherwise sinks each kernel-argument load to its first use (a
+  // scalar round trip of its own after the barrier), now they come with the
+  // first load clause and its one wait.
+  asm volatile("" ::"s"(C.H), "s"(C.W), "s"(C.max_steps), "s"(C.goal_tol), "s"(action_v), "s"(S.episode),
+               "s"(k_steps_arg));
+  // one HBM round trip before the first barrier: the env's state, its first
+  // action and the wall-mask entry
   double2 q = make_double2(0.0, 0.0), g = q, a0d = q;
   float2 a0f = make_float2(0.0f, 0.0f);
   int32_t el = 0, task = 1;
   uint32_t ep = 0;
   if (live) {
-    if (kF64) a0d = reinterpret_cast<const double2*>(action_v)[i];
-    else a0f = reinterpret_cast<const float2*>(action_v)[i];
-    q = reinterpret_cast<const double2*>(S.qpos)[i];
-    g = reinterpret_cast<const double2*>(S.goal)[i];
-    el = S.elapsed[i];
+    q = *env_elem<kPlain>(reinterpret_cast<const double2*>(S.qpos), i);
+    if (kF64) a0d = *env_elem<kPlain>(reinterpret_cast<const double2*>(action_v), i);
+    else a0f = *env_elem<kPlain>(reinterpret_cast<const float2*>(action_v), i);
+    g = *env_elem<kPlain>(reinterpret_cast<const double2*>(S.goal), i);
+    el = *env_elem<kPlain>(static_cast<const int32_t*>(S.elapsed), i);
   }
+  const uint16_t nbv = C.nbmask[threadIdx.x];
+#ifdef OGBX_STAGE_STAMPS
+  // the wait is the stamped build's own: the product waits where it first
+  // uses each value
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  OGBX_PS_AT(1);
+  path_stamp_store(0, ps_t0);
+#endif
   nbmask_commit(nb_s, nbv);
+  OGBX_PS_AT(2);
   if (!live) return;
   // task and episode counter are read only by an auto-reset or a teleport:
   // fetched here (their round trip hides under the physics) for the envs that
   // can end this step -- TimeLimit, or within goal_tol + 2 of the goal (a step
   // moves |0.2 a| <= 0.29 for actions in the action space) -- and lazily by
   // any other env that does end (an out-of-space action)
-  bool have_te = k_steps > 1 || P.n_tp_in > 0 || el + 1 >= P.max_steps;
+  bool have_te = k_steps > 1 || n_tp_in > 0 || el + 1 >= C.max_steps;
   {
-    const double ddx = q.x - g.x, ddy = q.y - g.y, lim = P.goal_tol + 2.0;
+    const double ddx = q.x - g.x, ddy = q.y - g.y, lim = C.goal_tol + 2.0;
     have_te |= ddx * ddx + ddy * ddy <= lim * lim;
   }
   if (have_te) {
-    ep = S.episode[i];
-    task = S.task[i];
+    ep = *env_elem<kPlain>(static_cast<const uint32_t*>(S.episode), i);
+    task = *env_elem<kPlain>(static_cast<const int32_t*>(S.task), i);
   }
-  const uint64_t gi = (uint64_t)(i + P.env_base);
+  const uint64_t gi = (uint64_t)(i + C.env_base);
   double x = q.x, y = q.y, gx = g.x, gy = g.y;
   bool reset_any = false;  // goal / episode change only on an auto-reset
   bool done = false;       // kUntilDone: this env's episode has ended
@@ -307,7 +395,7 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
     if (kUntilDone) {
       if (__all(done)) break;  // wave-uniform early exit (ballot over live lanes)
     }
-    const int64_t o = (int64_t)k * n + i;
+    const int64_t o = kPlain ? i : (int64_t)k * n + i;
     double dx, dy;
     if (kF64) {
       const double2 a = k == 0 ? a0d : reinterpret_cast<const double2*>(action_v)[o];
@@ -319,14 +407,26 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
       dy = (double)(0.2f * a.y);
     }
     bool succ = false;
-    if (P.success_pre) succ = goal_reached(x, y, gx, gy, P.goal_tol);
+    if (C.success_pre) succ = goal_within(x, y, gx, gy, C.goal_s2max);
     x = x + dx;
     y = y + dy;
-    point_step_as(pm, nb_s, P.H, P.W, &x, &y);
-    if (!P.success_pre) succ = goal_reached(x, y, gx, gy, P.goal_tol);
+    if constexpr (kPlain) {
+      // k_steps_arg is 1 here (maze_step_launch), so this loop runs once, but
+      // with a trip count the compiler cannot see: LLVM builds the stages'
+      // 64-bit constants once, in a loop's preheader, only if there is a loop
+      // to hoist them out of (the k loop of the generic instantiations).  As
+      // straight-line code each of the 20 stage blocks rebuilt its own (16
+      // s_mov_b32 per stage): the stages of a median wave took 13.5 k cycles
+      // instead of 11.9 k (profiles/step_path_ab.txt).
+#pragma unroll 1
+      for (int32_t rep = 0; rep < k_steps_arg; ++rep) point_step_as(pm, nb_s, C.H, C.W, &x, &y);
+    } else {
+      point_step_as(pm, nb_s, C.H, C.W, &x, &y);
+    }
+    if (!C.success_pre) succ = goal_within(x, y, gx, gy, C.goal_s2max);
     const double ox = x, oy = y;  // ob is taken before a teleport (maze.py:437-451)
-    if (P.n_tp_in > 0) {
-      for (int t = 0; t < P.n_tp_in; ++t) {
+    if (n_tp_in > 0) {
+      for (int t = 0; t < n_tp_in; ++t) {
         if (goal_reached(x, y, P.tp_in[t][0], P.tp_in[t][1], P.tp_radius * 1.5)) {
           u32x4 c = philox4x32_10({(uint32_t)gi, ep, 0x100u + (uint32_t)el, (uint32_t)(gi >> 32)},
                                   k0 ^ kTagMazeTeleport, k1);
@@ -338,35 +438,37 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
       }
     }
     float rew = succ ? 1.0f : 0.0f;
-    if (P.reward_task_id > 0) rew -= 1.0f;
-    const bool term = succ && P.terminate_at_goal;
+    if (C.reward_task_id > 0) rew -= 1.0f;
+    const bool term = succ && C.terminate_at_goal;
     el += 1;
-    const bool trunc = el >= P.max_steps;
+    const bool trunc = el >= C.max_steps;
     const bool write = writer && (!kUntilDone || !done);
     if (write) {
-      __builtin_nontemporal_store(rew, &reward[o]);
-      __builtin_nontemporal_store((uint8_t)term, &terminated[o]);
-      __builtin_nontemporal_store((uint8_t)trunc, &truncated[o]);
-      __builtin_nontemporal_store((uint8_t)succ, &success[o]);
+      __builtin_nontemporal_store(rew, env_elem<kPlain>(reward, o));
+      __builtin_nontemporal_store((uint8_t)term, env_elem<kPlain>(terminated, o));
+      __builtin_nontemporal_store((uint8_t)trunc, env_elem<kPlain>(truncated, o));
+      __builtin_nontemporal_store((uint8_t)succ, env_elem<kPlain>(success, o));
     }
+    OGBX_PS_AT(8);
     double wx = ox, wy = oy;
     if (auto_reset && (term || trunc)) {
       if (!have_te) {
-        ep = S.episode[i];
-        task = S.task[i];
+        ep = *env_elem<kPlain>(static_cast<const uint32_t*>(S.episode), i);
+        task = *env_elem<kPlain>(static_cast<const int32_t*>(S.task), i);
         have_te = true;
       }
-      if (final_obs != nullptr && writer) reinterpret_cast<double2*>(final_obs)[o] = make_double2(ox, oy);
+      if (final_obs != nullptr && writer)
+        *env_elem<kPlain>(reinterpret_cast<double2*>(final_obs), o) = make_double2(ox, oy);
       ep += 1u;
       reset_any = true;
       double r[4];
       reset_draws(gi, ep, k0, k1, r);
-      reset_one(P, task, nullptr, r, x, y, gx, gy);
+      reset_from_task(pm, P.tasks[task - 1], C.add_noise_to_goal, r, x, y, gx, gy);
       el = 0;
       wx = x;
       wy = y;
     }
-    if (write) __builtin_nontemporal_store(f64x2{wx, wy}, reinterpret_cast<f64x2*>(obs) + o);
+    if (write) __builtin_nontemporal_store(f64x2{wx, wy}, env_elem<kPlain>(reinterpret_cast<f64x2*>(obs), o));
     if (kUntilDone && !done) {
       taken = k + 1;
       done = term || trunc;
@@ -382,19 +484,21 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
     if (writer) steps_taken[i] = taken;
   }
   if (!writer) return;  // a copy lane (kEpwReplicate)
+  OGBX_PS_AT(9);
   // non-temporal stores for the state and the outputs (nothing in the launch
   // reads them back): 11.37 -> 11.29 us per launch at N = 65,536 (A/B,
   // four rounds), no change at 8,192
-  __builtin_nontemporal_store(f64x2{x, y}, reinterpret_cast<f64x2*>(S.qpos) + i);
-  __builtin_nontemporal_store(el, &S.elapsed[i]);
+  __builtin_nontemporal_store(f64x2{x, y}, env_elem<kPlain>(reinterpret_cast<f64x2*>(S.qpos), i));
+  __builtin_nontemporal_store(el, env_elem<kPlain>(S.elapsed, i));
   if (reset_any) {
-    reinterpret_cast<double2*>(S.goal)[i] = make_double2(gx, gy);
-    S.episode[i] = ep;
+    *env_elem<kPlain>(reinterpret_cast<double2*>(S.goal), i) = make_double2(gx, gy);
+    *env_elem<kPlain>(S.episode, i) = ep;
   }
+  OGBX_PS_AT(10);
 #ifdef OGBX_WAVE_STAMPS
   {
     const unsigned long long t1 = wall_clock64(), c1 = clock64();
-    const int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t w = ((int64_t)blockIdx.x * kStepBlock + threadIdx.x) >> 6;
     if ((threadIdx.x & 63) == 0 && w < 4096) {
       g_wave_stamps[4 * w + 0] = ws_t0;
       g_wave_stamps[4 * w + 1] = t1;
@@ -719,6 +823,8 @@ ogbx_status ogbx_maze_create(const char* maze_type, int64_t n_envs, int32_t devi
     (void)hipFuncSetAttribute((const void*)maze_step_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_pad);
     (void)hipFuncSetAttribute((const void*)maze_step_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_pad);
     (void)hipFuncSetAttribute((const void*)maze_step_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_pad);
+    (void)hipFuncSetAttribute((const void*)maze_step_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_pad);
+    (void)hipFuncSetAttribute((const void*)maze_step_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_pad);
     (void)hipFuncSetAttribute((const void*)point_physics_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_pad);
     (void)hipFuncSetAttribute((const void*)point_physics_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_pad);
   }
@@ -785,6 +891,21 @@ ogbx_status ogbx_maze_create(const char* maze_type, int64_t n_envs, int32_t devi
   build_bfs(P, bfs);
   if (herr == hipSuccess) herr = hipMalloc(&e->Pd, sizeof(MazeParams));
   if (herr == hipSuccess) herr = hipMemcpy(e->Pd, &P, sizeof(MazeParams), hipMemcpyHostToDevice);
+  if (herr == hipSuccess) {
+    MazeStepConsts& C = e->C;
+    C.nbmask = e->Pd->nbmask;  // an address in the device copy, not dereferenced here
+    C.env_base = P.env_base;
+    C.goal_tol = P.goal_tol;
+    C.goal_s2max = goal_s2max(P.goal_tol);
+    C.H = P.H;
+    C.W = P.W;
+    C.max_steps = P.max_steps;
+    C.n_tp_in = P.n_tp_in;
+    C.success_pre = P.success_pre;
+    C.terminate_at_goal = P.terminate_at_goal;
+    C.reward_task_id = P.reward_task_id;
+    C.add_noise_to_goal = P.add_noise_to_goal;
+  }
   if (herr == hipSuccess) herr = hipMalloc(&e->bfs, bfs.size() * sizeof(int16_t));
   if (herr == hipSuccess)
     herr = hipMemcpy(e->bfs, bfs.data(), bfs.size() * sizeof(int16_t), hipMemcpyHostToDevice);
@@ -863,6 +984,18 @@ ogbx_status ogbx_diag_wave_stages(unsigned long long* out) {
   OGBX_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_stages), 4096 * 8 * sizeof(unsigned long long)));
   static unsigned long long z[4096 * 8];
   OGBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wave_stages), z, sizeof(z)));
+  return OGBX_OK;
+}
+#endif
+
+#ifdef OGBX_STAGE_STAMPS
+// Diagnostic build only: the per-wave boundary stamps of the last launch
+// (point_physics.h g_path_stamps, 16 words per wave), then cleared.
+ogbx_status ogbx_diag_path_stamps(unsigned long long* out) {
+  OGBX_HIP(hipDeviceSynchronize());
+  OGBX_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_path_stamps), 4096 * 16 * sizeof(unsigned long long)));
+  static unsigned long long z[4096 * 16];
+  OGBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_path_stamps), z, sizeof(z)));
   return OGBX_OK;
 }
 #endif
@@ -947,14 +1080,12 @@ ogbx_status maze_step_launch(ogbx_maze_t e, const void* action, int32_t action_i
   seed_key(e->seed, kTagMazeReset, &k0, &k1);
   const int epw = e->epw;
   dim3 grid(grid_for(e->n * (64 / (epw & 0xFF)), kStepBlock)), block(kStepBlock);
-  if (action_is_f64)
-    hipLaunchKernelGGL((maze_step_kernel<true, false>), grid, block, e->lds_pad, (hipStream_t)stream, e->Pd, e->S,
-                       e->n, action, k_steps, obs, reward, terminated, truncated, success,
-                       final_obs, auto_reset, k0, k1, epw, nullptr);
-  else
-    hipLaunchKernelGGL((maze_step_kernel<false, false>), grid, block, e->lds_pad, (hipStream_t)stream, e->Pd, e->S,
-                       e->n, action, k_steps, obs, reward, terminated, truncated, success,
-                       final_obs, auto_reset, k0, k1, epw, nullptr);
+  // env.step's launch takes the plain instantiation; every other setting the generic one
+  const bool plain = k_steps == 1 && epw == 64 && e->C.n_tp_in == 0 && e->n <= kPlainMaxEnvs;
+  auto* kern = action_is_f64 ? (plain ? maze_step_kernel<true, false, true> : maze_step_kernel<true, false, false>)
+                             : (plain ? maze_step_kernel<false, false, true> : maze_step_kernel<false, false, false>);
+  hipLaunchKernelGGL(kern, grid, block, e->lds_pad, (hipStream_t)stream, e->C, e->S, action, e->n, obs, reward,
+                     terminated, truncated, success, auto_reset, k_steps, final_obs, k0, k1, epw, e->Pd, nullptr);
   OGBX_LAUNCHED("maze_step_kernel");
   return OGBX_OK;
 }
@@ -1082,13 +1213,13 @@ ogbx_status ogbx_maze_rollout_until_done(ogbx_maze_t e, const void* action, int3
   const int epw = e->epw;
   dim3 grid(grid_for(e->n * (64 / (epw & 0xFF)), kStepBlock)), block(kStepBlock);
   if (action_is_f64)
-    hipLaunchKernelGGL((maze_step_kernel<true, true>), grid, block, e->lds_pad, (hipStream_t)stream, e->Pd, e->S,
-                       e->n, action, k_steps, obs, reward, terminated, truncated, success, nullptr, 0, k0, k1,
-                       epw, steps_taken);
+    hipLaunchKernelGGL((maze_step_kernel<true, true>), grid, block, e->lds_pad, (hipStream_t)stream, e->C, e->S,
+                       action, e->n, obs, reward, terminated, truncated, success, 0, k_steps, nullptr, k0, k1,
+                       epw, e->Pd, steps_taken);
   else
-    hipLaunchKernelGGL((maze_step_kernel<false, true>), grid, block, e->lds_pad, (hipStream_t)stream, e->Pd, e->S,
-                       e->n, action, k_steps, obs, reward, terminated, truncated, success, nullptr, 0, k0, k1,
-                       epw, steps_taken);
+    hipLaunchKernelGGL((maze_step_kernel<false, true>), grid, block, e->lds_pad, (hipStream_t)stream, e->C, e->S,
+                       action, e->n, obs, reward, terminated, truncated, success, 0, k_steps, nullptr, k0, k1,
+                       epw, e->Pd, steps_taken);
   OGBX_LAUNCHED("maze_step_kernel");
   return OGBX_OK;
 }

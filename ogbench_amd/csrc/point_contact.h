@@ -540,6 +540,8 @@ __device__ uint32_t g_mask_trace[65536 * 40];
 // and the build is slower than the product; the parts' proportions are the
 // reading, not their sum.
 __device__ unsigned long long g_wave_stages[4096 * 8];
+#endif
+#if defined(OGBX_STAGE_STAMPS) && OGBX_STAGE_STAMPS != 2
 #define OGBX_SS_AT(acc)                              \
   do {                                               \
     __builtin_amdgcn_sched_barrier(0);               \
@@ -720,6 +722,7 @@ __device__ __forceinline__ void contact_loop_local(const PointModel& pm, double&
   PieceWeights pw;
   piece_weights(act, pw);
   const int nstage = 4 * pm.nsub;
+  OGBX_PS_AT(4);
 #pragma unroll 20
   for (int e = 0; e < nstage; ++e) {
     const int st = e & 3;
@@ -844,11 +847,13 @@ __device__ __forceinline__ void contact_loop_local(const PointModel& pm, double&
     }
     if (more) c = cn;
     OGBX_SS_AT(ss5);
+    if (e == 0) OGBX_PS_AT(5);
   }
+  OGBX_PS_AT(6);
 #ifdef OGBX_STAGE_STAMPS
   {
     const unsigned long long b = __ballot(1);
-    const unsigned w = (unsigned)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const unsigned w = (unsigned)((blockIdx.x * kStepBlock + threadIdx.x) >> 6);
     if (w < 4096 && (int)(threadIdx.x & 63) == __ffsll((long long)b) - 1) {
       unsigned long long* o = g_wave_stages + 8 * w;
       o[0] = ss0, o[1] = ss1, o[2] = ss2, o[3] = ss3, o[4] = ss4, o[5] = ss5, o[6] = ss6, o[7] = ss7;
@@ -861,7 +866,7 @@ __device__ __forceinline__ void contact_loop_local(const PointModel& pm, double&
 #ifdef OGBX_WAVE_STAMPS
   {
     const unsigned long long b = __ballot(1);
-    const unsigned w = (unsigned)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const unsigned w = (unsigned)((blockIdx.x * kStepBlock + threadIdx.x) >> 6);
     if (w < 4096 && (int)(threadIdx.x & 63) == __ffsll((long long)b) - 1) g_wave_paths[w] = g_wpath;
   }
 #endif
@@ -908,6 +913,7 @@ __device__ __forceinline__ int point_step_as(const PointModel& pm, const uint16_
   bool slow;
   const uint32_t v1 = contact_flags(pm, fr, x, y, &slow);
   bool in_contact = v1 != 0;
+  OGBX_PS_AT(3);
   if (__builtin_expect(__any(slow), 0)) {
     bool generic;
     in_contact = stage_contacts(pm, wall, H, W, x, y, fr, c, &generic) != 0;
@@ -931,6 +937,7 @@ __device__ __forceinline__ int point_step_as(const PointModel& pm, const uint16_
     x = bail ? xf : x;
     y = bail ? yf : y;
   }
+  OGBX_PS_AT(7);
   *px = in_contact ? x : x0 + 0.0;
   *py = in_contact ? y : y0 + 0.0;
   return in_contact ? 1 : 0;

@@ -81,6 +81,37 @@ __device__ __forceinline__ double fast_recip(double d) {
   return r;
 }
 
+// The step/physics kernels run 256-thread blocks (locomaze.hip: one thread per
+// entry of the wall-mask table).
+constexpr int kStepBlock = 256;
+
+#ifdef OGBX_STAGE_STAMPS
+// Diagnostic build only: s_memtime at the outer boundaries of one step of
+// maze_step_kernel, per wave (first active lane stores; 16 words per wave,
+// scripts/probe_step_path.py names them): 0 wave entry, 1 prologue loads
+// landed, 2 after the barrier, 3 role_frame / contact_flags done, 4 entry to
+// the lean loop, 5 after its first stage, 6 loop exit, 7 after the bail check,
+// 8 after the success / reward block, 9 before the final stores, 10 after
+// them.  Consecutive differences are the parts of the wave's stamped lifetime.
+// -DOGBX_STAGE_STAMPS=2 takes only these (the per-stage stamps of
+// point_contact.h, six per stage, slow the loop they measure).
+__device__ unsigned long long g_path_stamps[4096 * 16];
+__device__ __forceinline__ void path_stamp_store(int k, unsigned long long t) {
+  const unsigned long long b = __ballot(1);
+  const unsigned w = (unsigned)((blockIdx.x * kStepBlock + threadIdx.x) >> 6);
+  if (w < 4096 && (int)(threadIdx.x & 63) == __ffsll((long long)b) - 1) g_path_stamps[16 * w + k] = t;
+}
+#define OGBX_PS_AT(k)                                           \
+  do {                                                          \
+    __builtin_amdgcn_sched_barrier(0);                          \
+    const unsigned long long _t = __builtin_amdgcn_s_memtime(); \
+    __builtin_amdgcn_sched_barrier(0);                          \
+    path_stamp_store(k, _t);                                    \
+  } while (0)
+#else
+#define OGBX_PS_AT(k) ((void)0)
+#endif
+
 #ifdef OGBX_WAVE_STAMPS
 // Diagnostic build only: per-wave path counters of the current step, packed
 // [cold-block entries | iteration trips << 20 | band stages << 40], kept in a
