@@ -150,10 +150,12 @@ __device__ __forceinline__ void role_tangents(Contacts& c) {
 // D = a0 - a1 (as doubles).
 // A2 = a0 + a1 + a2 and C2 = a2 of slot 2 feed the lean loop's double-angle
 // form of the corner terms (local_piece_min).
+// (S3, T3, D3: the fourth slot of the kG = 4 generic evaluation.)
 struct PieceWeights {
-  double S0, T0, D0, S1, T1, D1, S2, T2, D2, A2, C2;
+  double S0, T0, D0, S1, T1, D1, S2, T2, D2, A2, C2, S3, T3, D3;
 };
 
+template <int kG = kMaxContacts>
 __device__ __forceinline__ void piece_weights(uint32_t A, PieceWeights& p) {
   auto one = [&](int s, double& S, double& T, double& D) {
     const int a0 = (A >> (3 * s)) & 1, a1 = (A >> (3 * s + 1)) & 1, a2 = (A >> (3 * s + 2)) & 1;
@@ -164,6 +166,7 @@ __device__ __forceinline__ void piece_weights(uint32_t A, PieceWeights& p) {
   one(0, p.S0, p.T0, p.D0);
   one(1, p.S1, p.T1, p.D1);
   one(2, p.S2, p.T2, p.D2);
+  if (kG > 3) one(3, p.S3, p.T3, p.D3);
   const int a2 = (A >> 8) & 1;
   p.A2 = (double)(((A >> 6) & 1) + ((A >> 7) & 1) + a2);
   p.C2 = (double)a2;
@@ -191,11 +194,11 @@ __device__ __forceinline__ void slot_res(const Contacts& c, int s, double ux, do
 
 // Active-edge mask at u (residual < 0: a + b < 0, a - b < 0, a < 0); the
 // bits of invalid slots are meaningless (callers mask them).
-template <bool kRoles>
+template <bool kRoles, int kG = kMaxContacts>
 __device__ __forceinline__ uint32_t edge_mask(const Contacts& c, double ux, double uy) {
   uint32_t act = 0;
 #pragma unroll
-  for (int s = 0; s < kMaxContacts; ++s) {
+  for (int s = 0; s < (kRoles ? kMaxContacts : kG); ++s) {
     double a, b;
     slot_res<kRoles>(c, s, ux, uy, &a, &b);
     act |= (a < -b ? 1u : 0u) << (3 * s);
@@ -207,7 +210,7 @@ __device__ __forceinline__ uint32_t edge_mask(const Contacts& c, double ux, doub
 
 // Minimiser of the quadratic piece with weights p (see the header).
 // mbv = m B v (= M cu).
-template <bool kRoles>
+template <bool kRoles, int kG = kMaxContacts>
 __device__ __forceinline__ void piece_min(const PointModel& pm, const Contacts& c, const PieceWeights& p,
                                           double mbvx, double mbvy, double* ux, double* uy) {
 #pragma clang fp contract(fast)
@@ -239,11 +242,11 @@ __device__ __forceinline__ void piece_min(const PointModel& pm, const Contacts& 
     r0 = mbvx;
     r1 = mbvy;
 #pragma unroll
-    for (int s = 0; s < kMaxContacts; ++s) {
+    for (int s = 0; s < kG; ++s) {
       const ContactSlot& k = slot_of(c, s);
-      const double S = k.w * (s == 0 ? p.S0 : (s == 1 ? p.S1 : p.S2));
-      const double T = k.w * (s == 0 ? p.T0 : (s == 1 ? p.T1 : p.T2));
-      const double D = k.w * (s == 0 ? p.D0 : (s == 1 ? p.D1 : p.D2));
+      const double S = k.w * (s == 0 ? p.S0 : (s == 1 ? p.S1 : (s == 2 ? p.S2 : p.S3)));
+      const double T = k.w * (s == 0 ? p.T0 : (s == 1 ? p.T1 : (s == 2 ? p.T2 : p.T3)));
+      const double D = k.w * (s == 0 ? p.D0 : (s == 1 ? p.D1 : (s == 2 ? p.D2 : p.D3)));
       h00 += S * (k.nx * k.nx) + T * (k.tx * k.tx) + 2.0 * D * (k.nx * k.tx);
       h11 += S * (k.ny * k.ny) + T * (k.ty * k.ty) + 2.0 * D * (k.ny * k.ty);
       h01 += S * (k.nx * k.ny) + T * (k.tx * k.ty) + D * (k.nx * k.ty + k.ny * k.tx);
@@ -260,7 +263,7 @@ __device__ __forceinline__ void piece_min(const PointModel& pm, const Contacts& 
 // backtracking from cu (monotone, globally convergent).  Never seen in the
 // bench states.  (Out of line, with the generic collider, the kernel is 3.5x
 // smaller but 60 % slower: the call ABI costs registers.)
-template <bool kRoles>
+template <bool kRoles, int kG = kMaxContacts>
 __device__ __forceinline__ void armijo_newton(const PointModel& pm, const Contacts& c, uint32_t valid, double cux,
                                               double cuy, double* ux_out, double* uy_out) {
   // explicit rows for eval_piece: tangents of role slots, invalid slots zeroed
@@ -269,11 +272,13 @@ __device__ __forceinline__ void armijo_newton(const PointModel& pm, const Contac
   if (!(valid & kSlotBits)) zero_slot(z.s0);
   if (!(valid & (kSlotBits << 3))) zero_slot(z.s1);
   if (!(valid & (kSlotBits << 6))) zero_slot(z.s2);
+  constexpr int kSlots = kRoles ? kMaxContacts : kG;
+  if (kSlots > 3 && !(valid & (kSlotBits << 9))) zero_slot(z.s3);
   double g[2], h[3], f;
   double ux = cux, uy = cuy;
 #pragma unroll 1
   for (int it = 0; it < 64; ++it) {
-    eval_piece(pm, z, cux, cuy, ux, uy, g, h, &f);
+    eval_piece<kSlots>(pm, z, cux, cuy, ux, uy, g, h, &f);
     const double idet = 1.0 / (h[0] * h[2] - h[1] * h[1]);
     const double px = -(h[2] * g[0] - h[1] * g[1]) * idet;
     const double py = -(h[0] * g[1] - h[1] * g[0]) * idet;
@@ -282,7 +287,7 @@ __device__ __forceinline__ void armijo_newton(const PointModel& pm, const Contac
     double t = 1.0, g2[2], h2[3], f2;
 #pragma unroll 1
     for (int bt = 0; bt < 60; ++bt) {
-      eval_piece(pm, z, cux, cuy, ux + t * px, uy + t * py, g2, h2, &f2);
+      eval_piece<kSlots>(pm, z, cux, cuy, ux + t * px, uy + t * py, g2, h2, &f2);
       if (f2 <= f + 1e-6 * t * slope) break;
       t *= 0.5;
     }
@@ -300,7 +305,7 @@ __device__ __forceinline__ void armijo_newton(const PointModel& pm, const Contac
 // On return *act_io is the mask of the converged build (pw its weights).
 // One iteration for every lane (straight line), more only while some lane's
 // mask still changes; after kFullIters, the damped Newton finishes the lane.
-template <bool kRoles>
+template <bool kRoles, int kG = kMaxContacts>
 __device__ __forceinline__ void solve_active_set(const PointModel& pm, const Contacts& c, uint32_t valid,
                                                  double vx, double vy, uint32_t* act_io, PieceWeights& pw,
                                                  double* ux_out, double* uy_out) {
@@ -309,8 +314,8 @@ __device__ __forceinline__ void solve_active_set(const PointModel& pm, const Con
   const double mbvx = mB * vx, mbvy = mB * vy;
   uint32_t A = *act_io;
   double ux, uy;
-  piece_min<kRoles>(pm, c, pw, mbvx, mbvy, &ux, &uy);
-  uint32_t A2 = edge_mask<kRoles>(c, ux, uy);
+  piece_min<kRoles, kG>(pm, c, pw, mbvx, mbvy, &ux, &uy);
+  uint32_t A2 = edge_mask<kRoles, kG>(c, ux, uy);
   bool done = ((A2 ^ A) & valid) == 0u;
   OGBX_WSTAT(9, true);
   OGBX_WSTAT(13, !done);
@@ -319,16 +324,16 @@ __device__ __forceinline__ void solve_active_set(const PointModel& pm, const Con
     for (int it = 0; it < kFullIters && !done; ++it) {
       OGBX_STAT(4);
       A = A2 & valid;
-      piece_weights(A, pw);
-      piece_min<kRoles>(pm, c, pw, mbvx, mbvy, &ux, &uy);
-      A2 = edge_mask<kRoles>(c, ux, uy);
+      piece_weights<kG>(A, pw);
+      piece_min<kRoles, kG>(pm, c, pw, mbvx, mbvy, &ux, &uy);
+      A2 = edge_mask<kRoles, kG>(c, ux, uy);
       done = ((A2 ^ A) & valid) == 0u;
     }
     if (!done) {
       OGBX_STAT(5);
-      armijo_newton<kRoles>(pm, c, valid, mbvx / pm.M, mbvy / pm.M, &ux, &uy);
-      A = edge_mask<kRoles>(c, ux, uy) & valid;
-      piece_weights(A, pw);
+      armijo_newton<kRoles, kG>(pm, c, valid, mbvx / pm.M, mbvy / pm.M, &ux, &uy);
+      A = edge_mask<kRoles, kG>(c, ux, uy) & valid;
+      piece_weights<kG>(A, pw);
     }
   }
   *act_io = A;
@@ -342,6 +347,7 @@ __device__ __forceinline__ void solve_active_set(const PointModel& pm, const Con
 // *generic tells which evaluation THIS LANE uses: the choice is per lane (the
 // wave runs both evaluations when it holds both kinds), so a lane's result
 // never depends on which envs share its wavefront.
+template <int kG = kMaxContacts>
 __device__ __forceinline__ uint32_t stage_contacts(const PointModel& pm, const uint16_t* wall, int H, int W,
                                                    double x, double y, const RoleFrame& fr, Contacts& c,
                                                    bool* generic) {
@@ -356,8 +362,8 @@ __device__ __forceinline__ uint32_t stage_contacts(const PointModel& pm, const u
       const double reach = pm.box_hxy - pm.radius - 1e-9;
       const int sx = lx >= reach ? 1 : (lx <= -reach ? -1 : 0);
       const int sy = ly >= reach ? 1 : (ly <= -reach ? -1 : 0);
-      const int n = collide_walls_generic(pm, wall, H, W, x, y, fr.fi, fr.fj, sx, sy, c);
-      valid = n >= 3 ? 0x1FFu : (n == 2 ? 0x3Fu : (n == 1 ? 0x7u : 0u));
+      const int n = collide_walls_generic<kG>(pm, wall, H, W, x, y, fr.fi, fr.fj, sx, sy, c);
+      valid = n >= 4 ? 0xFFFu : (n == 3 ? 0x1FFu : (n == 2 ? 0x3Fu : (n == 1 ? 0x7u : 0u)));
     }
   }
   return valid;
@@ -368,6 +374,7 @@ __device__ __forceinline__ uint32_t stage_contacts(const PointModel& pm, const u
 // refresh when the centre leaves its cell's half size, the generic collider
 // per lane, and the damped-Newton safety net.  Takes the lanes the lean loop
 // hands over (point_step_as).
+template <int kG = kMaxContacts>
 __device__ __forceinline__ void contact_loop(const PointModel& pm, const uint16_t* wall, int H, int W, double& x,
                                              double& y, RoleFrame fr, Contacts c, uint32_t valid, bool generic) {
   const double h = pm.h;
@@ -376,9 +383,12 @@ __device__ __forceinline__ void contact_loop(const PointModel& pm, const uint16_
   double sqx = 0.0, sqy = 0.0, svx = 0.0, svy = 0.0;
   // first stage: v = 0, so the mask at u = cu = 0 (every edge of a penetrating
   // contact) starts the iteration one step ahead of the empty set
-  uint32_t act = edge_mask<true>(c, 0.0, 0.0) & valid;
+  // (at u = 0 the residuals are a = kp, b = 0 in either layout)
+  uint32_t act = edge_mask<true>(c, 0.0, 0.0);
+  if (kG > 3 && generic) act |= c.s3.kp < 0.0 ? kSlotBits << 9 : 0u;
+  act &= valid;
   PieceWeights pw;
-  piece_weights(act, pw);
+  piece_weights<kG>(act, pw);
   const int nstage = 4 * pm.nsub;
   // (by 4, not 20, for the rare full loop: the RK coefficients stay constants
   // and the kernel's code shrinks by 1.3 MB; 11.55 -> 11.48 us per launch at
@@ -392,14 +402,14 @@ __device__ __forceinline__ void contact_loop(const PointModel& pm, const uint16_
       if (__builtin_expect(__any(stale), 0)) {
         if (stale) role_frame(pm, wall, H, W, qsx, qsy, fr);
       }
-      valid = stage_contacts(pm, wall, H, W, qsx, qsy, fr, c, &generic);
+      valid = stage_contacts<kG>(pm, wall, H, W, qsx, qsy, fr, c, &generic);
     }
     double fx, fy;
     {
 #pragma clang fp contract(fast)
       double ux, uy;
-      if (generic) solve_active_set<false>(pm, c, valid, vsx, vsy, &act, pw, &ux, &uy);
-      else solve_active_set<true>(pm, c, valid, vsx, vsy, &act, pw, &ux, &uy);
+      if (generic) solve_active_set<false, kG>(pm, c, valid, vsx, vsy, &act, pw, &ux, &uy);
+      else solve_active_set<true, kG>(pm, c, valid, vsx, vsy, &act, pw, &ux, &uy);
       fx = ux - pm.B * vsx;
       fy = uy - pm.B * vsy;
     }
@@ -895,6 +905,32 @@ __device__ __forceinline__ uint32_t contact_flags(const PointModel& pm, const Ro
   return (cX ? kSlotBits : 0u) | (cY ? kSlotBits << 3 : 0u) | (cD ? kSlotBits << 6 : 0u);
 }
 
+// The step of a lane whose centre starts inside a wall cell or off the map:
+// the full loop with the four-slot generic evaluation (kMaxGeneric), out of
+// line.  One body for every kernel, so such a lane's result is the same in
+// each of them; the call sits in a cold block at the head of point_step_as
+// and the inlined loops stay at three slots.
+struct WalledStep {
+  double x, y;
+  int contact;
+};
+
+__device__ __noinline__ WalledStep point_step_walled(const uint16_t* wall, int H, int W, double x, double y) {
+  constexpr PointModel pm = kPointModel;
+  RoleFrame fr;
+  role_frame(pm, wall, H, W, x, y, fr);
+  Contacts c;
+  bool generic;
+  const uint32_t valid = stage_contacts<kMaxGeneric>(pm, wall, H, W, x, y, fr, c, &generic);
+  WalledStep r;
+  r.contact = valid != 0u ? 1 : 0;
+  double xs = x, ys = y;
+  if (valid != 0u) contact_loop<kMaxGeneric>(pm, wall, H, W, xs, ys, fr, c, valid, generic);
+  r.x = valid != 0u ? xs : x + 0.0;
+  r.y = valid != 0u ? ys : y + 0.0;
+  return r;
+}
+
 // One PointEnv physics step: qpos (after the action) -> qpos after 5 RK4
 // substeps.  Returns 1 if a wall contact was present at the start.
 // Free lanes of a wave with a contact lane run the loop too (their result is
@@ -913,20 +949,31 @@ __device__ __forceinline__ int point_step_as(const PointModel& pm, const uint16_
   bool slow;
   const uint32_t v1 = contact_flags(pm, fr, x, y, &slow);
   bool in_contact = v1 != 0;
+  // in a wall cell or off the map: the out-of-line step, whose result the
+  // selects below keep for the lane whatever the loops compute for it (it
+  // runs them alongside when its wave does; in a wave with an on-edge lane
+  // stage_contacts flags it again)
+  const bool walled = fr.slow;
+  WalledStep ws = {x, y, 0};
+  if (__builtin_expect(__any(walled), 0)) {
+    if (walled) ws = point_step_walled(wall, H, W, x, y);
+  }
+  slow = slow & !walled;
+  in_contact = in_contact & !walled;
   OGBX_PS_AT(3);
   if (__builtin_expect(__any(slow), 0)) {
     bool generic;
     in_contact = stage_contacts(pm, wall, H, W, x, y, fr, c, &generic) != 0;
   }
   if (!__any(in_contact)) {
-    *px = x + 0.0;
-    *py = y + 0.0;
-    return 0;
+    *px = walled ? ws.x : x + 0.0;
+    *py = walled ? ws.y : y + 0.0;
+    return walled ? ws.contact : 0;
   }
   const double x0 = x, y0 = y;
   bool bail;
   contact_loop_local(pm, x, y, fr, &bail);  // a slow lane's values are discarded
-  bail |= slow;
+  bail = (bail | slow) & !walled;
   OGBX_WSTAT(14, bail);
   if (__builtin_expect(__any(bail), 0)) {
     double xf = x0, yf = y0;
@@ -938,9 +985,9 @@ __device__ __forceinline__ int point_step_as(const PointModel& pm, const uint16_
     y = bail ? yf : y;
   }
   OGBX_PS_AT(7);
-  *px = in_contact ? x : x0 + 0.0;
-  *py = in_contact ? y : y0 + 0.0;
-  return in_contact ? 1 : 0;
+  *px = walled ? ws.x : (in_contact ? x : x0 + 0.0);
+  *py = walled ? ws.y : (in_contact ? y : y0 + 0.0);
+  return walled ? ws.contact : (in_contact ? 1 : 0);
 }
 
 }  // namespace ogbx

@@ -139,8 +139,14 @@ __device__ unsigned long long g_phys_stats[32];
 // A sphere whose centre lies in an empty cell touches at most 3 wall boxes
 // (two faces + the corner box between them).  States with the centre deep in
 // a wall (contact through a box z face = two pseudo-contacts) are unreachable
-// from any reset; there, contacts beyond 3 are dropped.
+// from any reset; in the inlined loops, contacts beyond 3 are dropped.
+// kMaxGeneric: a centre inside a wall cell, within the radius of a corner
+// where four wall cells meet, touches its own box, both side boxes and the
+// diagonal one -- every box the generic collider tests.  Lanes that start in
+// a wall cell or off the map take point_step_walled (point_contact.h), whose
+// generic evaluation holds that fourth contact (slot s3, kG = 4 below).
 constexpr int kMaxContacts = 3;
+constexpr int kMaxGeneric = 4;
 
 struct ContactSlot {
   double nx, ny;  // Jn: gradient of dist (slide dofs)
@@ -149,17 +155,18 @@ struct ContactSlot {
   double w;       // D = 1/R of one edge
 };
 
-// Three named slots, not an array: LLVM cannot turn a write to a runtime slot
+// Named slots, not an array: LLVM cannot turn a write to a runtime slot
 // into a dynamically indexed store, so the contacts never leave VGPRs.
+// s3 is touched by the kG = 4 generic evaluation alone.
 struct Contacts {
   int n;
   bool roles;  // slots hold the role layout of collide_in_frame (s0 x face, s1 y face)
-  ContactSlot s0, s1, s2;
+  ContactSlot s0, s1, s2, s3;
 };
 
 // Static slot access (k is a compile-time constant in every unrolled loop).
 __device__ __forceinline__ const ContactSlot& slot_of(const Contacts& c, int k) {
-  return k == 0 ? c.s0 : (k == 1 ? c.s1 : c.s2);
+  return k == 0 ? c.s0 : (k == 1 ? c.s1 : (k == 2 ? c.s2 : c.s3));
 }
 
 // Impedance-dependent (D, K*imp*dist) of a contact at `dist` (MuJoCo
@@ -196,6 +203,7 @@ __device__ __forceinline__ double clamp_box(double p, double h) {
 // Store one contact into slot `slot` (runtime index, per-field selects: a
 // branchy store would be merged by SimplifyCFG into one store through a
 // selected address -> scratch).
+template <int kG = kMaxContacts>
 __device__ __forceinline__ void add_contact(const PointModel& pm, Contacts& c, int slot, double dist,
                                             double nx, double ny, double tx, double ty) {
   double D, kp;
@@ -211,6 +219,7 @@ __device__ __forceinline__ void add_contact(const PointModel& pm, Contacts& c, i
   put(c.s0, slot == 0);
   put(c.s1, slot == 1);
   put(c.s2, slot == 2);
+  if (kG > 3) put(c.s3, slot == 3);
 }
 
 __device__ __forceinline__ void zero_slot(ContactSlot& k) {
@@ -222,12 +231,14 @@ __device__ __forceinline__ void zero_slot(ContactSlot& k) {
 // the box frame; boxes axis aligned, margin 0) of the own cell's box and the
 // x-side, y-side and diagonal neighbours, in that order.  One rolled loop with
 // one contact-append site keeps this path small (it is inlined).
+template <int kG = kMaxContacts>
 __device__ __forceinline__ int collide_walls_generic(const PointModel& pm, const uint16_t* nbmask,
                                                      int H, int W, double x, double y, double fi,
                                                      double fj, int sx, int sy, Contacts& c) {
   zero_slot(c.s0);
   zero_slot(c.s1);
   zero_slot(c.s2);
+  if (kG > 3) zero_slot(c.s3);
   const double cx = fj * pm.unit - pm.off_x, cy = fi * pm.unit - pm.off_y;
   const double u = pm.unit, hx = pm.box_hxy, hz = pm.box_hz;
   int nc = 0;
@@ -247,7 +258,7 @@ __device__ __forceinline__ int collide_walls_generic(const PointModel& pm, const
     const double clz = clamp_box(pz, hz);
     const double tx = clx - px, ty = cly - py, tz = clz - pz;
     const double d2 = tx * tx + ty * ty + tz * tz;
-    if (d2 > pm.r2_hi || nc >= kMaxContacts) continue;  // certainly d - r > 0
+    if (d2 > pm.r2_hi || nc >= kG) continue;  // certainly d - r > 0
     double dist, nx, ny, ax, ay;  // ax, ay: tangent of the (first) contact
     int ne = 1;
     bool second = false;          // z face: two pseudo-contacts (tangents e_x, e_y)
@@ -297,9 +308,9 @@ __device__ __forceinline__ int collide_walls_generic(const PointModel& pm, const
       }
     }
 #pragma unroll 1
-    for (int e = 0; e < ne && nc < kMaxContacts; ++e) {
+    for (int e = 0; e < ne && nc < kG; ++e) {
       const bool z2 = second && e == 1;
-      add_contact(pm, c, nc, dist, nx, ny, z2 ? 0.0 : ax, z2 ? 1.0 : ay);
+      add_contact<kG>(pm, c, nc, dist, nx, ny, z2 ? 0.0 : ax, z2 ? 1.0 : ay);
       ++nc;
     }
   }
@@ -314,8 +325,9 @@ __device__ __forceinline__ int collide_walls_generic(const PointModel& pm, const
 //   M = m + Df, cu = m B v / M, and for contact s with a = n.u + kp, b = t.u:
 //   e0: r = a + b (weight w), e1: r = a - b (w), e2: r = a (2w).
 // Gradient, Hessian and value of f at u for explicit contact rows (the
-// damped-Newton safety net of point_contact.h armijo_newton): every slot, an
-// empty slot an all-zero row (r = 0, never active, no contribution).
+// damped-Newton safety net of point_contact.h armijo_newton): the first kSlots
+// slots, an empty slot an all-zero row (r = 0, never active, no contribution).
+template <int kSlots = kMaxContacts>
 __device__ __forceinline__ void eval_piece(const PointModel& pm, const Contacts& c, double cux, double cuy,
                                            double ux, double uy, double* g, double* h, double* fval) {
 #pragma clang fp contract(fast)
@@ -325,7 +337,7 @@ __device__ __forceinline__ void eval_piece(const PointModel& pm, const Contacts&
   h[0] = M; h[1] = 0.0; h[2] = M;
   double f = 0.5 * M * ((ux - cux) * (ux - cux) + (uy - cuy) * (uy - cuy));
 #pragma unroll
-  for (int s = 0; s < kMaxContacts; ++s) {
+  for (int s = 0; s < kSlots; ++s) {
     const ContactSlot& k = slot_of(c, s);
     const double a = k.nx * ux + k.ny * uy + k.kp;
     const double b = k.tx * ux + k.ty * uy;

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import contact_atlas
 import ogbench_amd
 from oracle import locomaze as orc
 
@@ -383,13 +384,12 @@ def test_results_do_not_depend_on_wavefront_composition(gpu):
     single-GPU run."""
     rng = np.random.RandomState(31)
     mp, _ = orc.tables('large')
-    free_cells, wall_cells = np.argwhere(mp == 0), np.argwhere(mp == 1)
+    free_cells = np.argwhere(mp == 0)
     n = 24000
     c = free_cells[rng.randint(len(free_cells), size=n)]
     q = np.stack([c[:, 1] * 4.0 - 4 + rng.uniform(-1.95, 1.95, n), c[:, 0] * 4.0 - 4 + rng.uniform(-1.95, 1.95, n)], 1)
     k = n // 50
-    wc = wall_cells[rng.randint(len(wall_cells), size=k)]
-    q[:k] = np.stack([wc[:, 1] * 4.0 - 4 + rng.uniform(-2, 2, k), wc[:, 0] * 4.0 - 4 + rng.uniform(-2, 2, k)], 1)
+    q[:k] = contact_atlas.in_wall_cell('large', k, seed=32)  # uniform over the wall cells
     a = rng.uniform(-1, 1, (n, 2)).astype(np.float32)
     perm = rng.permutation(n)
     env = _env(gpu, 1)
