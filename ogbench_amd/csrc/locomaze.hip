@@ -17,6 +17,7 @@
 //   xy_to_ij / ij_to_xy / add_noise  maze.py:552-567
 //   PointEnv.step   ogbench/locomaze/point.py:64-95
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -71,6 +72,45 @@ struct MazeStepConsts {
   int32_t success_pre, terminate_at_goal, reward_task_id, add_noise_to_goal;
 };
 
+// maze_step_kernel's arguments as they lie in the kernarg segment (each at its
+// natural alignment, in order): the plain step reads what its epilogue needs
+// from there after the physics instead of holding it in scalar registers
+// through the stages.  Keep in step with the kernel's parameter list.
+struct MazeStepArgs {
+  MazeStepConsts C;
+  MazeState S;
+  const void* action;
+  int64_t n;
+  double* obs;
+  float* reward;
+  uint8_t *terminated, *truncated, *success;
+  int32_t auto_reset, k_steps;
+  double* final_obs;
+  uint32_t k0, k1;
+  int32_t epw;
+  const MazeParams* Pp;
+  int32_t* steps_taken;
+};
+static_assert(offsetof(MazeStepArgs, S) == 0x40 && offsetof(MazeStepArgs, n) == 0x70 &&
+                  offsetof(MazeStepArgs, obs) == 0x78 && offsetof(MazeStepArgs, final_obs) == 0xa8 &&
+                  offsetof(MazeStepArgs, Pp) == 0xc0 && sizeof(MazeStepArgs) == 0xd0,
+              "MazeStepArgs mirrors maze_step_kernel's kernarg layout");
+
+// What a step needs after the physics.
+struct MazeStepTail {
+  int64_t n, env_base;
+  double goal_s2max;
+  int32_t max_steps, success_pre, terminate_at_goal, reward_task_id, add_noise_to_goal, auto_reset;
+  uint32_t k0, k1;
+  const MazeParams* Pp;
+  double *obs, *final_obs;
+  float* reward;
+  uint8_t *terminated, *truncated, *success;
+  double *qpos, *goal;
+  int32_t* elapsed;
+  uint32_t* episode;
+};
+
 }  // namespace ogbx
 
 struct ogbx_maze_env {
@@ -117,9 +157,11 @@ __device__ inline void stage_nbmask(const MazeParams& P, uint16_t* nb_s) {
 
 // The step/physics kernels run 256-thread blocks, one thread per entry of the
 // kMaxCells-entry wall-mask table: each thread loads its entry straight from
-// the table's address (no dependent read of H*W), issued together with the
-// env's state and action loads so that the whole prologue is one HBM round
-// trip; nbmask_commit stores it into LDS after them.
+// the table's address (no dependent read of H*W); nbmask_commit stores it
+// into LDS behind a block barrier.  In the built code this load is not part
+// of the state loads' clause: those sit in the `if (live)` exec branch and the
+// entry is loaded after the branch rejoins, a second round trip.  The plain
+// step (below) has neither the branch nor the barrier.
 static_assert(kMaxCells == kStepBlock, "one wall-mask entry per thread of a step block");
 
 __device__ __forceinline__ uint16_t nbmask_fetch(const MazeParams* Pp) { return Pp->nbmask[threadIdx.x]; }
@@ -128,6 +170,13 @@ __device__ __forceinline__ void nbmask_commit(uint16_t* nb_s, uint16_t v) {
   nb_s[threadIdx.x] = v;
   __syncthreads();
 }
+
+// The plain step keeps the table per wave instead: 64 lanes x 8 bytes are the
+// whole table, loaded and stored as uint64_t (may_alias: the physics reads the
+// same bytes as uint16_t).
+typedef uint64_t u64_alias __attribute__((may_alias));
+static_assert(kMaxCells * sizeof(uint16_t) == 64 * sizeof(uint64_t), "one 8-byte piece of the table per lane of a wave");
+static_assert(offsetof(MazeParams, nbmask) % sizeof(uint64_t) == 0, "the table is read in 8-byte pieces");
 
 // np.linalg.norm(xy - goal) <= tol with the 1-D OpenBLAS ddot rounding:
 // sqrt(fma(dy, dy, dx*dx)) (maze.py:487).
@@ -303,6 +352,35 @@ __device__ __forceinline__ T* env_elem(T* base, int64_t i) {
   }
 }
 
+// The tail's part of the arguments at *a (a MazeStepArgs in any address space).
+template <class ArgsPtr>
+__device__ __forceinline__ MazeStepTail step_tail(ArgsPtr a) {
+  MazeStepTail T;
+  T.n = a->n;
+  T.env_base = a->C.env_base;
+  T.goal_s2max = a->C.goal_s2max;
+  T.max_steps = a->C.max_steps;
+  T.success_pre = a->C.success_pre;
+  T.terminate_at_goal = a->C.terminate_at_goal;
+  T.reward_task_id = a->C.reward_task_id;
+  T.add_noise_to_goal = a->C.add_noise_to_goal;
+  T.auto_reset = a->auto_reset;
+  T.k0 = a->k0;
+  T.k1 = a->k1;
+  T.Pp = a->Pp;
+  T.obs = a->obs;
+  T.final_obs = a->final_obs;
+  T.reward = a->reward;
+  T.terminated = a->terminated;
+  T.truncated = a->truncated;
+  T.success = a->success;
+  T.qpos = a->S.qpos;
+  T.goal = a->S.goal;
+  T.elapsed = a->S.elapsed;
+  T.episode = a->S.episode;
+  return T;
+}
+
 // kPlain: the single env.step launch (maze_step_launch picks it for k_steps ==
 // 1, 64 envs per wave, no teleports, n <= kPlainMaxEnvs): k_steps, epw and the
 // teleport count are compile-time constants here, so the k loop, the teleport
@@ -320,7 +398,9 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
   OGBX_POINT_MODEL(pm, P);
   const int32_t k_steps = kPlain ? 1 : k_steps_arg;
   const int32_t n_tp_in = kPlain ? 0 : C.n_tp_in;
-  __shared__ uint16_t nb_s[kMaxCells];
+  // the wall-mask table: one copy per block, or (kPlain) one per wave
+  __shared__ __attribute__((aligned(8))) uint16_t nb_s[kPlain ? kStepBlock / 64 * kMaxCells : kMaxCells];
+  const uint16_t* nb = nb_s;
 #ifdef OGBX_WAVE_STAMPS
   const unsigned long long ws_t0 = wall_clock64(), ws_c0 = clock64();
 #endif
@@ -331,22 +411,36 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
   bool writer = true;
   int64_t i;
   bool live;
+  // The constants the step reads before the physics, asked for here: the
+  // compiler otherwise sinks each kernel-argument load to its first use (a
+  // scalar round trip of its own), now they come with the first load clause
+  // and its one wait.  The plain step asks for all it reads before the
+  // physics, n included: its exit test below then costs no round trip of its
+  // own ahead of the others.
+  if constexpr (kPlain) {
+    asm volatile("" ::"s"(n), "s"(C.nbmask), "s"(C.H), "s"(C.W), "s"(C.success_pre), "s"(C.goal_s2max), "s"(action_v),
+                 "s"(S.qpos), "s"(S.goal), "s"(S.elapsed), "s"(S.task), "s"(S.episode), "s"(k_steps_arg));
+  } else {
+    asm volatile("" ::"s"(C.H), "s"(C.W), "s"(C.max_steps), "s"(C.goal_tol), "s"(action_v), "s"(S.episode),
+                 "s"(k_steps_arg));
+  }
   if constexpr (kPlain) {
     const uint32_t t = blockIdx.x * kStepBlock + threadIdx.x;
-    i = t;
-    live = t < (uint32_t)n;
+    // a wave without an env leaves here (wave-uniform: lane 0 holds its first
+    // index); n >= 1 (ogbx_maze_create)
+    if ((uint32_t)__builtin_amdgcn_readfirstlane((int)t) >= (uint32_t)n) return;
+    // a lane past the last env steps a copy of env n - 1 and stores nothing:
+    // every choice of the step is per lane, so the copy takes the path its
+    // original takes anyway, and no load of the prologue sits under a branch
+    live = true;
+    writer = t < (uint32_t)n;
+    i = writer ? t : (uint32_t)n - 1u;
   } else {
     i = env_of_lane(epw, &writer);
     live = i >= 0 && i < n;
   }
-  // The constants the step reads before the physics, asked for here: the
-  // compiler otherwise sinks each kernel-argument load to its first use (a
-  // scalar round trip of its own after the barrier), now they come with the
-  // first load clause and its one wait.
-  asm volatile("" ::"s"(C.H), "s"(C.W), "s"(C.max_steps), "s"(C.goal_tol), "s"(action_v), "s"(S.episode),
-               "s"(k_steps_arg));
-  // one HBM round trip before the first barrier: the env's state, its first
-  // action and the wall-mask entry
+  // one HBM round trip: the env's state, its first action and the wall-mask
+  // table
   double2 q = make_double2(0.0, 0.0), g = q, a0d = q;
   float2 a0f = make_float2(0.0f, 0.0f);
   int32_t el = 0, task = 1;
@@ -358,32 +452,66 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
     g = *env_elem<kPlain>(reinterpret_cast<const double2*>(S.goal), i);
     el = *env_elem<kPlain>(static_cast<const int32_t*>(S.elapsed), i);
   }
-  const uint16_t nbv = C.nbmask[threadIdx.x];
-#ifdef OGBX_STAGE_STAMPS
-  // the wait is the stamped build's own: the product waits where it first
-  // uses each value
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  OGBX_PS_AT(1);
-  path_stamp_store(0, ps_t0);
-#endif
-  nbmask_commit(nb_s, nbv);
-  OGBX_PS_AT(2);
-  if (!live) return;
-  // task and episode counter are read only by an auto-reset or a teleport:
-  // fetched here (their round trip hides under the physics) for the envs that
-  // can end this step -- TimeLimit, or within goal_tol + 2 of the goal (a step
-  // moves |0.2 a| <= 0.29 for actions in the action space) -- and lazily by
-  // any other env that does end (an out-of-space action)
-  bool have_te = k_steps > 1 || n_tp_in > 0 || el + 1 >= C.max_steps;
-  {
-    const double ddx = q.x - g.x, ddy = q.y - g.y, lim = C.goal_tol + 2.0;
-    have_te |= ddx * ddx + ddy * ddy <= lim * lim;
-  }
-  if (have_te) {
+  bool have_te;
+  if constexpr (kPlain) {
+    // The plain step's prologue is one straight run of code, so that the
+    // physics loop's constant set-up (its preheader) is scheduled under these
+    // loads: task and episode counter (read only by an auto-reset) come with
+    // the clause instead of behind a branch on the loaded state, and each wave
+    // keeps a wall-mask table of its own -- every lane loads 8 of its 512
+    // bytes and stores them to the wave's LDS slice.  The LDS operations of one
+    // wave complete in order, so wave-scope ordering is all a lane needs to
+    // read what the others stored: no block barrier.
     ep = *env_elem<kPlain>(static_cast<const uint32_t*>(S.episode), i);
     task = *env_elem<kPlain>(static_cast<const int32_t*>(S.task), i);
+    have_te = true;
+    const uint64_t nbv = reinterpret_cast<const u64_alias*>(C.nbmask)[threadIdx.x & 63];
+#ifdef OGBX_STAGE_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    OGBX_PS_AT(1);
+    path_stamp_store(0, ps_t0);
+#endif
+    reinterpret_cast<u64_alias*>(nb_s)[threadIdx.x] = nbv;  // slice w = entries [256 w, 256 w + 256)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    nb = nb_s + (threadIdx.x >> 6) * kMaxCells;
+    OGBX_PS_AT(2);
+  } else {
+    const uint16_t nbv = C.nbmask[threadIdx.x];
+#ifdef OGBX_STAGE_STAMPS
+    // the wait is the stamped build's own: the product waits where it first
+    // uses each value
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    OGBX_PS_AT(1);
+    path_stamp_store(0, ps_t0);
+#endif
+    nbmask_commit(nb_s, nbv);
+    OGBX_PS_AT(2);
+    if (!live) return;
+    // task and episode counter are read only by an auto-reset or a teleport:
+    // fetched here (their round trip hides under the physics) for the envs that
+    // can end this step -- TimeLimit, or within goal_tol + 2 of the goal (a step
+    // moves |0.2 a| <= 0.29 for actions in the action space) -- and lazily by
+    // any other env that does end (an out-of-space action)
+    have_te = k_steps > 1 || n_tp_in > 0 || el + 1 >= C.max_steps;
+    {
+      const double ddx = q.x - g.x, ddy = q.y - g.y, lim = C.goal_tol + 2.0;
+      have_te |= ddx * ddx + ddy * ddy <= lim * lim;
+    }
+    if (have_te) {
+      ep = *env_elem<kPlain>(static_cast<const uint32_t*>(S.episode), i);
+      task = *env_elem<kPlain>(static_cast<const int32_t*>(S.task), i);
+    }
   }
-  const uint64_t gi = (uint64_t)(i + C.env_base);
+  // what the step reads after the physics: the arguments themselves, or
+  // (kPlain) their reload from the kernarg segment behind the physics
+  MazeStepTail T;
+  if constexpr (!kPlain) {
+    const MazeStepArgs A{C,  S,  action_v, n,   obs, reward, terminated, truncated,  success, auto_reset, k_steps_arg,
+                         final_obs, k0, k1, epw, Pp,  steps_taken};
+    T = step_tail(&A);
+  }
   double x = q.x, y = q.y, gx = g.x, gy = g.y;
   bool reset_any = false;  // goal / episode change only on an auto-reset
   bool done = false;       // kUntilDone: this env's episode has ended
@@ -417,13 +545,34 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
       // to hoist them out of (the k loop of the generic instantiations).  As
       // straight-line code each of the 20 stage blocks rebuilt its own (16
       // s_mov_b32 per stage): the stages of a median wave took 13.5 k cycles
-      // instead of 11.9 k (profiles/step_path_ab.txt).
+      // instead of 11.9 k (profiles/step_path_ab.txt).  Tested at the bottom:
+      // a guard ahead of the loop would be a branch between the prologue's
+      // loads and the preheader.
+      int32_t rep = 0;
 #pragma unroll 1
-      for (int32_t rep = 0; rep < k_steps_arg; ++rep) point_step_as(pm, nb_s, C.H, C.W, &x, &y);
+      do point_step_as(pm, nb, C.H, C.W, &x, &y);
+      while (++rep < k_steps_arg);
     } else {
-      point_step_as(pm, nb_s, C.H, C.W, &x, &y);
+      point_step_as(pm, nb, C.H, C.W, &x, &y);
     }
-    if (!C.success_pre) succ = goal_within(x, y, gx, gy, C.goal_s2max);
+    if constexpr (kPlain) {
+      // Held from the prologue, the epilogue's ~34 scalar registers of
+      // arguments squeezed the stages' constants out (rebuilt or spilled in
+      // every stage).  The pointer is laundered so that these loads cannot
+      // move up across the physics.
+      auto A = (const __attribute__((address_space(4))) MazeStepArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+      asm volatile("" : "+s"(A));
+      T = step_tail(A);
+      // asked for together: one scalar round trip, not one per first use
+      asm volatile("" ::"s"(T.n), "s"(T.env_base), "s"(T.goal_s2max), "s"(T.max_steps), "s"(T.success_pre),
+                   "s"(T.terminate_at_goal), "s"(T.reward_task_id), "s"(T.add_noise_to_goal), "s"(T.auto_reset),
+                   "s"(T.k0), "s"(T.k1), "s"(T.Pp));
+      asm volatile("" ::"s"(T.obs), "s"(T.final_obs), "s"(T.reward), "s"(T.terminated), "s"(T.truncated),
+                   "s"(T.success), "s"(T.qpos), "s"(T.goal), "s"(T.elapsed), "s"(T.episode));
+      writer = (uint32_t)(blockIdx.x * kStepBlock + threadIdx.x) < (uint32_t)T.n;
+    }
+    const uint64_t gi = (uint64_t)(i + T.env_base);
+    if (!T.success_pre) succ = goal_within(x, y, gx, gy, T.goal_s2max);
     const double ox = x, oy = y;  // ob is taken before a teleport (maze.py:437-451)
     if (n_tp_in > 0) {
       for (int t = 0; t < n_tp_in; ++t) {
@@ -438,37 +587,37 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
       }
     }
     float rew = succ ? 1.0f : 0.0f;
-    if (C.reward_task_id > 0) rew -= 1.0f;
-    const bool term = succ && C.terminate_at_goal;
+    if (T.reward_task_id > 0) rew -= 1.0f;
+    const bool term = succ && T.terminate_at_goal;
     el += 1;
-    const bool trunc = el >= C.max_steps;
+    const bool trunc = el >= T.max_steps;
     const bool write = writer && (!kUntilDone || !done);
     if (write) {
-      __builtin_nontemporal_store(rew, env_elem<kPlain>(reward, o));
-      __builtin_nontemporal_store((uint8_t)term, env_elem<kPlain>(terminated, o));
-      __builtin_nontemporal_store((uint8_t)trunc, env_elem<kPlain>(truncated, o));
-      __builtin_nontemporal_store((uint8_t)succ, env_elem<kPlain>(success, o));
+      __builtin_nontemporal_store(rew, env_elem<kPlain>(T.reward, o));
+      __builtin_nontemporal_store((uint8_t)term, env_elem<kPlain>(T.terminated, o));
+      __builtin_nontemporal_store((uint8_t)trunc, env_elem<kPlain>(T.truncated, o));
+      __builtin_nontemporal_store((uint8_t)succ, env_elem<kPlain>(T.success, o));
     }
     OGBX_PS_AT(8);
     double wx = ox, wy = oy;
-    if (auto_reset && (term || trunc)) {
+    if (T.auto_reset && (term || trunc)) {
       if (!have_te) {
-        ep = *env_elem<kPlain>(static_cast<const uint32_t*>(S.episode), i);
+        ep = *env_elem<kPlain>(static_cast<const uint32_t*>(T.episode), i);
         task = *env_elem<kPlain>(static_cast<const int32_t*>(S.task), i);
         have_te = true;
       }
-      if (final_obs != nullptr && writer)
-        *env_elem<kPlain>(reinterpret_cast<double2*>(final_obs), o) = make_double2(ox, oy);
+      if (T.final_obs != nullptr && writer)
+        *env_elem<kPlain>(reinterpret_cast<double2*>(T.final_obs), o) = make_double2(ox, oy);
       ep += 1u;
       reset_any = true;
       double r[4];
-      reset_draws(gi, ep, k0, k1, r);
-      reset_from_task(pm, P.tasks[task - 1], C.add_noise_to_goal, r, x, y, gx, gy);
+      reset_draws(gi, ep, T.k0, T.k1, r);
+      reset_from_task(pm, T.Pp->tasks[task - 1], T.add_noise_to_goal, r, x, y, gx, gy);
       el = 0;
       wx = x;
       wy = y;
     }
-    if (write) __builtin_nontemporal_store(f64x2{wx, wy}, env_elem<kPlain>(reinterpret_cast<f64x2*>(obs), o));
+    if (write) __builtin_nontemporal_store(f64x2{wx, wy}, env_elem<kPlain>(reinterpret_cast<f64x2*>(T.obs), o));
     if (kUntilDone && !done) {
       taken = k + 1;
       done = term || trunc;
@@ -488,11 +637,11 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
   // non-temporal stores for the state and the outputs (nothing in the launch
   // reads them back): 11.37 -> 11.29 us per launch at N = 65,536 (A/B,
   // four rounds), no change at 8,192
-  __builtin_nontemporal_store(f64x2{x, y}, env_elem<kPlain>(reinterpret_cast<f64x2*>(S.qpos), i));
-  __builtin_nontemporal_store(el, env_elem<kPlain>(S.elapsed, i));
+  __builtin_nontemporal_store(f64x2{x, y}, env_elem<kPlain>(reinterpret_cast<f64x2*>(T.qpos), i));
+  __builtin_nontemporal_store(el, env_elem<kPlain>(T.elapsed, i));
   if (reset_any) {
-    *env_elem<kPlain>(reinterpret_cast<double2*>(S.goal), i) = make_double2(gx, gy);
-    *env_elem<kPlain>(S.episode, i) = ep;
+    *env_elem<kPlain>(reinterpret_cast<double2*>(T.goal), i) = make_double2(gx, gy);
+    *env_elem<kPlain>(T.episode, i) = ep;
   }
   OGBX_PS_AT(10);
 #ifdef OGBX_WAVE_STAMPS
