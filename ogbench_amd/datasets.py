@@ -13,7 +13,12 @@ Batched, device-side counterparts of impls/utils/datasets.py (hliuson/ogbench):
   ATCDataset ~ ATCDataset (datasets.py:369-464): ``sample(batch_size, k,
                evaluation=False)`` returns ``observations`` and
                ``positive_observations``, k rows apart in one trajectory, in
-               one launch of ``atc_sample_kernel`` (include/ogbx_atc.h).
+               one launch of ``atc_sample_kernel`` (include/ogbx_atc.h);
+  ReplayBuffer ~ ReplayBuffer (datasets.py:86-146): ``create``,
+               ``create_from_initial_dataset``, ``add_transition``, ``clear``
+               and ``sample`` over the rows held so far; ``add_transitions`` /
+               ``add_step`` insert one row per env in one launch of
+               ``replay_insert_kernel`` (include/ogbx_replay.h).
 
 Every sample is ONE launch of ``gc_sample_kernel`` (libogbx): index draw,
 trajectory-end lookup, hindsight goal relabel and the row gathers of every
@@ -194,6 +199,23 @@ class AtcOutputs(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ('idxs', 'pick', 'crop_from', 'bad_count')]
 
 
+class ReplayInsertColumn(ctypes.Structure):
+    _fields_ = [
+        ('dst', ctypes.c_void_p),
+        ('src', ctypes.c_void_p),
+        ('alt', ctypes.c_void_p),
+        ('row_elems', ctypes.c_int64),
+        ('src_dtype', ctypes.c_int32),
+        ('dst_dtype', ctypes.c_int32),
+        ('op', ctypes.c_int32),
+        ('pad_', ctypes.c_int32),
+    ]
+
+
+REPLAY_MAX_COLS = 16  # OGBX_REPLAY_MAX_COLS
+REPLAY_OP_NONE, REPLAY_OP_ONE_MINUS = 0, 1  # ogbx_replay_op
+
+
 def _bind():
     L = _lib.lib()
     if not getattr(L, '_gc_bound', False):
@@ -262,6 +284,19 @@ def _bind():
             ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
             ctypes.c_uint64, ctypes.c_uint64, P(AtcOutputs), ctypes.c_void_p,
         ]
+        # include/ogbx_replay.h (likewise)
+        L.ogbx_replay_api_version.restype = ctypes.c_int32
+        L.ogbx_replay_api_version.argtypes = []
+        L.ogbx_replay_insert.restype = ctypes.c_int32
+        L.ogbx_replay_insert.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]
+        L.ogbx_replay_clear.restype = ctypes.c_int32
+        L.ogbx_replay_clear.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.ogbx_replay_sample.restype = ctypes.c_int32
+        L.ogbx_replay_sample.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint64,
+                                         ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L._gc_bound = True
     return L
 
@@ -1589,3 +1624,385 @@ class ATCDataset:
             out['_idxs'] = rec.pop('idxs')
             out['_draws'] = rec
         return out
+
+
+def _replay_dtypes():
+    torch = _torch()
+    # ogbx_replay_dtype
+    return {torch.bool: 0, torch.uint8: 1, torch.int32: 2, torch.int64: 3, torch.float32: 4, torch.float64: 5}
+
+
+class ReplayBuffer(Dataset):
+    """Replay buffer on the device (reference: datasets.py:86-146; used by
+    data_gen_scripts/main_sac.py:66-137): a ``Dataset`` whose rows are written
+    by batched ring inserts and drawn uniformly from the rows held so far.
+
+    ``create``, ``create_from_initial_dataset``, ``max_size``, ``size``,
+    ``pointer``, ``add_transition`` and ``clear`` are the reference's.
+    ``add_transitions`` / ``add_step`` insert one row per env in ONE launch of
+    ``replay_insert_kernel``, ``sample`` / ``get_subset`` are ONE launch of
+    ``replay_sample_kernel`` (include/ogbx_replay.h).
+
+    The result of ``add_transitions`` is that of N sequential reference
+    ``add_transition`` calls in row order: with M rows kept, the j-th kept row
+    lands at ``(pointer + j) % max_size``, ``pointer' = (pointer + M) %
+    max_size`` and ``size' = max(size, min(pointer + M, max_size - 1))``.  The
+    last rule is the reference's quirk, kept on purpose: it computes ``size =
+    max(pointer, size)`` after the modulo, so ``size`` stops at ``max_size -
+    1`` and the buffer's last row is written but never drawn (a buffer of 5
+    after 7 adds has pointer 2 and size 4).
+
+    ``pointer`` and ``size`` live in a device-side header; no path of insert or
+    sample reads it back.  The host mirrors both exactly while no insert had a
+    ``keep`` mask; after a masked insert the ``pointer`` / ``size`` properties
+    read the header back, which synchronises with the stream (and makes the
+    mirror exact again).
+
+    ``create_from_initial_dataset`` sets ``pointer = size = len(init)``.  When
+    that equals ``max_size``, ``sample`` covers every row and the next add
+    raises ``IndexError``, as the reference does (a masked add too, whatever
+    its mask keeps: the host does not know the count).
+
+    Values are cast to the column's dtype as a NumPy assignment casts them,
+    for in-range values (sources bool, uint8, int32, int64, float32, float64;
+    columns uint8, int32, int64, float32, float64).  A buffer with a 'valids'
+    key is refused (the reference would draw from an empty ``valid_idxs``),
+    as are columns of unequal length.
+
+    ``sample`` draws with the plain sampler's Philox words: at one ``(seed,
+    call)`` a buffer of size s returns, bit for bit, what ``Dataset({k: v[:s]})
+    .sample`` returns.  An empty buffer raises ValueError when the host knows
+    the size is 0; when it does not (a masked insert came last), every sample
+    reads row 0 and the kernel adds the batch size to a device counter, read by
+    ``empty_draws()``.
+    """
+
+    SAC_KEYS = ('observations', 'actions', 'rewards', 'masks', 'next_observations')  # main_sac.py:115-123
+
+    @classmethod
+    def create(cls, transition, size, device=None, seed=None):
+        """Zero buffers ``[size, *shape]`` with the dtype of
+        ``np.array(example)`` (datasets.py:92-106): ``rewards=0.0`` gives a
+        float64 column."""
+        torch = _torch()
+        if device is None:
+            device = 'cuda'
+        size = operator.index(size)
+        if size <= 0:
+            raise ValueError(f'size must be > 0, got {size}')
+        cols = {}
+        for k, example in transition.items():
+            if isinstance(example, torch.Tensor):
+                shape, dtype = tuple(example.shape), example.dtype
+            else:
+                example = np.array(example)
+                shape, dtype = example.shape, torch.from_numpy(np.zeros(0, example.dtype)).dtype
+            cols[k] = torch.zeros((size,) + tuple(shape), dtype=dtype, device=device)
+        return cls(cols, device=device, seed=seed)
+
+    @classmethod
+    def create_from_initial_dataset(cls, init_dataset, size, device=None, seed=None):
+        """Buffers of ``size`` rows holding ``init_dataset`` in front, with
+        ``pointer = size = len(init_dataset)`` (datasets.py:108-125)."""
+        torch = _torch()
+        size = operator.index(size)
+        if device is None:
+            device = getattr(init_dataset, 'device', 'cuda')
+        init = {k: _to_device(v, device) for k, v in init_dataset.items()}
+        n = max(len(v) for v in init.values())
+        if size <= 0 or n > size:
+            raise ValueError(f'the initial dataset has {n} rows, the buffer {size}')
+        cols = {}
+        for k, v in init.items():
+            cols[k] = torch.zeros((size,) + tuple(v.shape[1:]), dtype=v.dtype, device=v.device)
+            cols[k][: len(v)] = v
+        rb = cls(cols, device=device, seed=seed)
+        rb._set_header(n, n)
+        return rb
+
+    def __init__(self, data=(), device=None, seed=None, **kw):
+        torch = _torch()
+        data = dict(data, **kw)
+        if 'valids' in data:
+            raise ValueError("a ReplayBuffer cannot have a 'valids' column (the reference would draw from an "
+                             'empty valid_idxs)')
+        self._hdr = None
+        super().__init__(data, device=device)
+        lens = {len(v) for v in self.values()}
+        if len(lens) != 1:
+            raise ValueError(f'every column of a ReplayBuffer needs the same number of rows, got {sorted(lens)}')
+        self.max_size = lens.pop()
+        self._L = _bind()
+        self._dtype_code = _replay_dtypes()
+        self._hdr = torch.zeros(4, dtype=torch.int64, device=self.device)  # OGBX_REPLAY_HEADER_WORDS
+        self._empty = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._parity = 0
+        self._h_pointer = self._h_size = 0
+        self._known = True
+        self._seed = int(seed) if seed is not None else None
+        self._calls = 0
+        self._ins_cache = {}
+        self._out_cache = {}
+        self._out_gen = self._gen
+        self._dev_idx = self.device.index
+        self._raw_stream = torch._C._cuda_getCurrentRawStream  # hipStream_t of the current stream, as an int
+
+    _next_seed = GCDataset._next_seed
+
+    # ------------------------------------------------------------------ header
+    def _set_header(self, pointer, size):
+        torch = _torch()
+        pointer, size = operator.index(pointer), operator.index(size)
+        if not (0 <= pointer <= self.max_size and 0 <= size <= self.max_size):
+            raise ValueError(f'pointer and size must lie in [0, {self.max_size}]')
+        row = torch.tensor([pointer, size, pointer, size], dtype=torch.int64)
+        self._hdr.copy_(row.to(self.device))
+        self._h_pointer, self._h_size, self._known = pointer, size, True
+
+    def _read_header(self):
+        if not self._known:
+            h = self._hdr.cpu()  # synchronises with the stream
+            self._h_pointer, self._h_size = int(h[2 * self._parity]), int(h[2 * self._parity + 1])
+            self._known = True
+
+    @property
+    def size(self):
+        self._read_header()
+        return self._h_size
+
+    @size.setter
+    def size(self, value):
+        if self._hdr is None:  # Dataset.__init__'s row count: max_size
+            return
+        self._read_header()
+        self._set_header(self._h_pointer, value)
+
+    @property
+    def pointer(self):
+        self._read_header()
+        return self._h_pointer
+
+    @pointer.setter
+    def pointer(self, value):
+        self._read_header()
+        self._set_header(value, self._h_size)
+
+    def clear(self):
+        """size = pointer = 0, on the stream (datasets.py:144-146); the rows
+        stay where they are."""
+        _lib.check(self._L.ogbx_replay_clear(_lib.ptr(self._hdr), _lib.stream_of(self.device)), 'replay_clear')
+        self._h_pointer = self._h_size = 0
+        self._known = True
+
+    def empty_draws(self):
+        """Samples drawn so far while the buffer was empty and the host did not
+        know it (each read row 0).  Reads the device counter: synchronises."""
+        return int(self._empty.item())
+
+    # ------------------------------------------------------------------ inserts
+    def _source(self, key, v, n):
+        """One leaf of an insert as a contiguous device tensor of n rows."""
+        torch = _torch()
+        if not isinstance(v, torch.Tensor):
+            v = torch.as_tensor(np.ascontiguousarray(v))
+        if v.device != self.device:
+            v = v.to(self.device)
+        if v.dtype not in self._dtype_code:
+            raise ValueError(f'{key!r}: unsupported source dtype {v.dtype}')
+        col = self[key]
+        if v.dim() == 0 or v.shape[0] != n or tuple(v.shape[1:]) != tuple(col.shape[1:]):
+            raise ValueError(f'{key!r}: expected shape {(n,) + tuple(col.shape[1:])}, got {tuple(v.shape)}')
+        return v if v.is_contiguous() else v.contiguous()
+
+    def _mask(self, name, m, n):
+        torch = _torch()
+        if m is None:
+            return None
+        if not isinstance(m, torch.Tensor):
+            m = torch.as_tensor(np.ascontiguousarray(m))
+        if m.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'{name} must be bool or uint8, got {m.dtype}')
+        if m.device != self.device:
+            m = m.to(self.device)
+        if m.dim() != 1 or not m.is_contiguous():
+            m = m.reshape(-1).contiguous()
+        if m.shape[0] != n:
+            raise ValueError(f'{name} must have {n} entries, got {m.shape[0]}')
+        return m  # the kernel reads bytes; torch's bool bytes are 0 / 1
+
+    def _insert(self, specs, n, keep, alt_select):
+        """specs: (key, src, alt or None, op) per column, already staged by
+        ``_source``.  One launch; the host mirror follows when no mask."""
+        if n > self.max_size:
+            raise ValueError(f'{n} rows in one insert exceed max_size {self.max_size} (two rows would race for one '
+                             'slot)')
+        if n == 0:
+            return
+        if self._known and self._h_pointer >= self.max_size:
+            raise IndexError(f'index {self._h_pointer} is out of bounds for axis 0 with size {self.max_size}')
+        key = (n, keep.data_ptr() if keep is not None else 0, alt_select.data_ptr() if alt_select is not None else 0,
+               self._gen) + tuple((k, s.data_ptr(), s.dtype, a.data_ptr() if a is not None else 0, op)
+                                  for k, s, a, op in specs)
+        arr = self._ins_cache.get(key)
+        if arr is None:
+            code = self._dtype_code
+            cols = []
+            for k, s, a, op in specs:
+                col = self[k]
+                if len(col) != self.max_size or not col.is_contiguous() or col.device != self.device:
+                    raise ValueError(f'buffer column {k!r} was replaced by one of another length, layout or device')
+                if col.dtype not in code or col.dtype is _torch().bool:
+                    raise ValueError(f'{k!r}: unsupported column dtype {col.dtype}')
+                if a is not None and a.dtype != s.dtype:
+                    raise ValueError(f'{k!r}: the alternative source has dtype {a.dtype}, the source {s.dtype}')
+                row = col[0].numel() if col.dim() > 1 else 1
+                cols.append(ReplayInsertColumn(col.data_ptr(), s.data_ptr(), a.data_ptr() if a is not None else None,
+                                               row, code[s.dtype], code[col.dtype], op, 0))
+            if len(cols) > REPLAY_MAX_COLS:
+                raise ValueError(f'at most {REPLAY_MAX_COLS} columns per insert, got {len(cols)}')
+            arr = (ReplayInsertColumn * len(cols))(*cols)
+            if len(self._ins_cache) >= 8:
+                self._ins_cache.clear()
+            self._ins_cache[key] = arr
+        st = self._L.ogbx_replay_insert(self._hdr.data_ptr(), self._parity, self.max_size, arr, len(arr), n,
+                                        _lib.ptr(keep), _lib.ptr(alt_select), self._raw_stream(self._dev_idx))
+        if st:
+            _lib.check(st, 'replay_insert')
+        self._parity ^= 1
+        if keep is not None:
+            self._known = False
+        elif self._known:
+            self._h_pointer, self._h_size = self._after(self._h_pointer, self._h_size, n, self.max_size)
+
+    @staticmethod
+    def _after(pointer, size, m, max_size):
+        """(pointer, size) after m >= 1 sequential reference adds: size' is the
+        largest pointer value visited, max(size, min(pointer + m, max_size - 1))
+        in every state the buffer reaches by itself (size >= pointer)."""
+        end = pointer + m
+        top = end if end < max_size else (max_size - 1 if pointer < max_size - 1 else m - 1)
+        return end % max_size, max(size, top)
+
+    def _check_keys(self, keys):
+        if set(keys) != set(self.keys()):
+            raise ValueError(f'the transition has keys {sorted(keys)}, the buffer {sorted(self.keys())}')
+
+    def add_transitions(self, batch, keep=None):
+        """Insert one row per env: every leaf of ``batch`` has a leading N.
+        ``keep`` (bool / uint8 ``[N]``): only the kept rows are added, in row
+        order.  N > max_size and keys that differ from the buffer's raise
+        ValueError."""
+        self._check_keys(batch)
+        first = next(iter(batch.values()))
+        n = len(first)
+        specs = [(k, self._source(k, batch[k], n), None, REPLAY_OP_NONE) for k in self]
+        self._insert(specs, n, self._mask('keep', keep, n), None)
+
+    def add_transition(self, transition):
+        """One transition whose leaves have no batch axis (datasets.py:134-142)."""
+        torch = _torch()
+        self._check_keys(transition)
+        batch = {}
+        for k, v in transition.items():
+            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+            batch[k] = v.reshape((1,) + tuple(self[k].shape[1:]))
+        self.add_transitions(batch)
+
+    def add_step(self, observations, actions, rewards, terminated, next_observations, final_observation=None,
+                 done=None, keep=None):
+        """Insert what a vectorized env's ``step`` returned as the reference's
+        SAC transitions (main_sac.py:115-123) in one launch:
+        ``masks = 1 - terminated`` and ``next_observations`` taken from
+        ``final_observation`` (``info['final_observation']`` of an
+        ``auto_reset=True`` env) where ``done`` (bool / uint8 ``[N]``,
+        terminated | truncated) is set.  The buffer's keys must be
+        ``SAC_KEYS``.
+
+        ``observations`` must be a tensor the caller still owns: the env's
+        observation view is overwritten by the step that produced
+        ``next_observations``, so pass a copy taken before that step."""
+        self._check_keys(self.SAC_KEYS)
+        if (final_observation is None) != (done is None):
+            raise ValueError('final_observation and done go together')
+        n = len(observations)
+        src = dict(observations=observations, actions=actions, rewards=rewards, masks=terminated,
+                   next_observations=next_observations)
+        alt = self._source('next_observations', final_observation, n) if final_observation is not None else None
+        specs = []
+        for k in self:
+            specs.append((k, self._source(k, src[k], n), alt if k == 'next_observations' else None,
+                          REPLAY_OP_ONE_MINUS if k == 'masks' else REPLAY_OP_NONE))
+        self._insert(specs, n, self._mask('keep', keep, n), self._mask('done', done, n))
+
+    # ----------------------------------------------------------------- sampling
+    def _batch(self, B, record_idxs):
+        torch = _torch()
+        out, cols = {}, []
+
+        def add(src_key, dst_key, select):
+            src = self[src_key]
+            if len(src) != self.max_size or not src.is_contiguous() or src.device != self.device:
+                raise ValueError(f'buffer column {src_key!r} was replaced by one of another length, layout or device')
+            dst = torch.empty((B,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
+            out[dst_key] = dst
+            row_bytes = (src[0].numel() if src.dim() > 1 else 1) * src.element_size()
+            cols.append(GcColumn(src.data_ptr(), dst.data_ptr(), row_bytes, select, 0))
+
+        for k in self.keys():
+            add(k, k, 0)
+        if 'next_observations' not in self:
+            add('observations', 'next_observations', 1)  # datasets.py:81-82
+        if len(cols) > REPLAY_MAX_COLS:
+            raise ValueError(f'at most {REPLAY_MAX_COLS} columns per sample, got {len(cols)}')
+        idx = torch.empty(B, dtype=torch.int64, device=self.device) if record_idxs else None
+        if record_idxs:
+            out['_idxs'] = idx
+        return out, (GcColumn * len(cols))(*cols), len(cols), idx
+
+    def sample(self, batch_size, idxs=None, out=None, record_idxs=False):
+        """Dataset.sample (datasets.py:72-83) over rows ``[0, size)``, one
+        launch: every column at the drawn (or given) rows, in the buffer's key
+        order; without a ``next_observations`` column,
+        ``next_observations = observations[min(idx + 1, size - 1)]`` with the
+        CURRENT size.  Explicit ``idxs`` are clamped into ``[0, max_size)``.
+
+        out: a batch returned by an earlier call with the same batch_size and
+        record_idxs (and no idxs): refilled in place, stream ordered, and
+        returned.
+        record_idxs: also return the rows used (``out['_idxs']``).
+        """
+        torch = _torch()
+        B = int(batch_size)
+        ix = None
+        if idxs is not None:
+            ix = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
+            if ix.numel() != B:
+                raise ValueError(f'idxs must have {B} entries, got {ix.numel()}')
+        elif self._known and self._h_size == 0:
+            raise ValueError('cannot sample from an empty ReplayBuffer')
+        if self._out_gen != self._gen:  # a column was replaced
+            self._out_cache.clear()
+            self._out_gen = self._gen
+        hit = self._out_cache.get(id(out)) if (out is not None and ix is None) else None
+        if hit is not None and hit[0] is out and hit[1] == (B, record_idxs):
+            arr, ncols, idx_out = hit[2]
+        else:
+            out, arr, ncols, idx_out = self._batch(B, record_idxs)
+            if ix is None:
+                if len(self._out_cache) >= 2:
+                    self._out_cache.clear()
+                self._out_cache[id(out)] = (out, (B, record_idxs), (arr, ncols, idx_out))
+        seed, call = self._next_seed()
+        st = self._L.ogbx_replay_sample(self._hdr.data_ptr(), self._parity, self.max_size, arr, ncols, B,
+                                        _lib.ptr(ix), seed, call, _lib.ptr(idx_out), self._empty.data_ptr(),
+                                        self._raw_stream(self._dev_idx))
+        if st:
+            _lib.check(st, 'replay_sample')
+        return out
+
+    def get_subset(self, idxs):
+        return self.sample(len(idxs), idxs=idxs)
+
+    def get_random_idxs(self, num_idxs):
+        """Uniform rows of ``[0, size)`` (datasets.py:65-70)."""
+        return self.sample(num_idxs, record_idxs=True)['_idxs']
