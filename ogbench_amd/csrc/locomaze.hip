@@ -406,6 +406,9 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
 #endif
 #ifdef OGBX_STAGE_STAMPS
   const unsigned long long ps_t0 = __builtin_amdgcn_s_memtime();
+#if OGBX_STAGE_STAMPS == 2
+  const unsigned long long ps_r0 = wall_clock64();  // words 11, 12: s_memrealtime beside the first and last stamp
+#endif
   __builtin_amdgcn_sched_barrier(0);
 #endif
   bool writer = true;
@@ -470,6 +473,9 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     OGBX_PS_AT(1);
     path_stamp_store(0, ps_t0);
+#if OGBX_STAGE_STAMPS == 2
+    path_stamp_store(11, ps_r0);
+#endif
 #endif
     reinterpret_cast<u64_alias*>(nb_s)[threadIdx.x] = nbv;  // slice w = entries [256 w, 256 w + 256)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -485,6 +491,9 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     OGBX_PS_AT(1);
     path_stamp_store(0, ps_t0);
+#if OGBX_STAGE_STAMPS == 2
+    path_stamp_store(11, ps_r0);
+#endif
 #endif
     nbmask_commit(nb_s, nbv);
     OGBX_PS_AT(2);
@@ -644,6 +653,9 @@ __global__ void __launch_bounds__(256) maze_step_kernel(
     *env_elem<kPlain>(T.episode, i) = ep;
   }
   OGBX_PS_AT(10);
+#if defined(OGBX_STAGE_STAMPS) && OGBX_STAGE_STAMPS == 2
+  path_stamp_store(12, wall_clock64());
+#endif
 #ifdef OGBX_WAVE_STAMPS
   {
     const unsigned long long t1 = wall_clock64(), c1 = clock64();

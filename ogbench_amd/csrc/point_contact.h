@@ -37,6 +37,7 @@
 // closest-point arithmetic).
 #pragma once
 
+#include "piece_weights.h"
 #include "point_physics.h"
 
 
@@ -147,30 +148,9 @@ __device__ __forceinline__ void role_tangents(Contacts& c) {
 }
 
 // Integer weights of a mask, per slot: S = a0 + a1 + 2 a2, T = a0 + a1,
-// D = a0 - a1 (as doubles).
-// A2 = a0 + a1 + a2 and C2 = a2 of slot 2 feed the lean loop's double-angle
-// form of the corner terms (local_piece_min).
-// (S3, T3, D3: the fourth slot of the kG = 4 generic evaluation.)
-struct PieceWeights {
-  double S0, T0, D0, S1, T1, D1, S2, T2, D2, A2, C2, S3, T3, D3;
-};
-
-template <int kG = kMaxContacts>
-__device__ __forceinline__ void piece_weights(uint32_t A, PieceWeights& p) {
-  auto one = [&](int s, double& S, double& T, double& D) {
-    const int a0 = (A >> (3 * s)) & 1, a1 = (A >> (3 * s + 1)) & 1, a2 = (A >> (3 * s + 2)) & 1;
-    T = (double)(a0 + a1);
-    D = (double)(a0 - a1);
-    S = (double)(a0 + a1 + 2 * a2);
-  };
-  one(0, p.S0, p.T0, p.D0);
-  one(1, p.S1, p.T1, p.D1);
-  one(2, p.S2, p.T2, p.D2);
-  if (kG > 3) one(3, p.S3, p.T3, p.D3);
-  const int a2 = (A >> 8) & 1;
-  p.A2 = (double)(((A >> 6) & 1) + ((A >> 7) & 1) + a2);
-  p.C2 = (double)a2;
-}
+// D = a0 - a1 (as doubles): PieceWeights, piece_weights (from the mask) and
+// piece_weights_from (from the edge activities) of piece_weights.h.
+static_assert(kMaxContacts == 3, "piece_weights' default slot count");
 
 // a = n.u + kp and b = t.u of slot s.
 template <bool kRoles>
@@ -637,14 +617,22 @@ __device__ __forceinline__ void local_corner_res(const LocalSlots& c, double ux,
   *b = fma(c.nx2, uy, -(c.ny2 * ux));
 }
 
-// Active-edge mask at U (local role layout, bits as edge_mask).
-__device__ __forceinline__ uint32_t local_edge_mask(const LocalSlots& c, double ux, double uy) {
+// Active-edge mask at U (local role layout, bits as edge_mask), with each
+// edge's activity as a double from the comparison that decides it: a Newton
+// step builds its piece weights from those (piece_weights_from), without
+// taking the mask apart again.  Where the stage settles at once nothing reads
+// them and they cost nothing.
+__device__ __forceinline__ uint32_t local_edge_mask(const LocalSlots& c, double ux, double uy, EdgeActs& e) {
   const double P = ux + uy, Q = ux - uy;
-  uint32_t m = (c.kp0 < P ? 1u : 0u) | (c.kp0 < Q ? 2u : 0u) | (c.kp0 < ux ? 4u : 0u);
-  m |= (c.kp1 < -Q ? 8u : 0u) | (c.kp1 < P ? 16u : 0u) | (c.kp1 < uy ? 32u : 0u);
   double a, b;
   local_corner_res(c, ux, uy, &a, &b);
-  m |= (a < -b ? 64u : 0u) | (a < b ? 128u : 0u) | (a < 0.0 ? 256u : 0u);
+  const bool on[9] = {c.kp0 < P, c.kp0 < Q, c.kp0 < ux, c.kp1 < -Q, c.kp1 < P, c.kp1 < uy, a < -b, a < b, a < 0.0};
+  uint32_t m = 0;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    m |= on[i] ? 1u << i : 0u;
+    e.a[i] = edge_on(on[i]);
+  }
   return m;
 }
 
@@ -728,9 +716,10 @@ __device__ __forceinline__ void contact_loop_local(const PointModel& pm, double&
   }
   // first stage: v = 0, so the mask at u = cu = 0 (every edge of a penetrating
   // contact) starts the iteration one step ahead of the empty set
-  uint32_t act = local_edge_mask(c, 0.0, 0.0);
+  EdgeActs ea;
+  uint32_t act = local_edge_mask(c, 0.0, 0.0, ea);
   PieceWeights pw;
-  piece_weights(act, pw);
+  piece_weights_from(ea, pw);
   const int nstage = 4 * pm.nsub;
   OGBX_PS_AT(4);
 #pragma unroll 20
@@ -767,16 +756,16 @@ __device__ __forceinline__ void contact_loop_local(const PointModel& pm, double&
     double ux, uy;
     local_piece_min(c, pw, vsx, vsy, &ux, &uy);
     OGBX_SS_AT(ss1);
-    uint32_t A2 = local_edge_mask(c, ux, uy);
+    uint32_t A2 = local_edge_mask(c, ux, uy, ea);
     if (e == 0) {
       // The first stage's warm start (every penetrating edge active) is exact
       // for a single contact but wrong for about half of the multi-contact
       // lanes (53 % of all active-set iterations of a step were this stage's):
       // one semismooth Newton step for every lane here, in line.
       act = A2;
-      piece_weights(act, pw);
+      piece_weights_from(ea, pw);
       local_piece_min(c, pw, vsx, vsy, &ux, &uy);
-      A2 = local_edge_mask(c, ux, uy);
+      A2 = local_edge_mask(c, ux, uy, ea);
     }
     // (round 5: the test as signs of the nine residual differences against
     // per-edge expected sign words, v_bitop3-merged -- 5 fewer instructions
@@ -794,7 +783,14 @@ __device__ __forceinline__ void contact_loop_local(const PointModel& pm, double&
     }
     int trips = 0;
 #endif
-    if (__builtin_expect(__any(!done), 0)) {
+    // (No __builtin_expect on this branch or on the rolled loop's below: 90 %
+    // of wave-stages skip them, but the launch waits for the waves that take
+    // them at 8 of their 20 stages.  With the hints LLVM moves the trips of all
+    // 20 stages behind the unrolled loop, tens of KB from the stage that enters
+    // them; without them each stage's trips follow its solve and the settled
+    // path branches over them.  The cheaper trips pay only in this layout:
+    // profiles/step_trips_ab.txt, which also says how to recheck it in the ISA.)
+    if (__any(!done)) {
       OGBX_WPATH(0);
       // Every lane runs the iteration (a wave-uniform loop): typically one or
       // two lanes of the wave flip an edge, and gfx950 issues a dependent
@@ -804,23 +800,32 @@ __device__ __forceinline__ void contact_loop_local(const PointModel& pm, double&
       // settled lane is at a fixed point (act == A2, pw = piece_weights(act)):
       // its rerun recomputes the same ux, uy and A2 bit for bit, so every
       // lane's result equals the per-lane loop's.
-#pragma unroll 1
-      for (int it = 0; it < kLeanIters; ++it) {
+      auto trip = [&](bool first) {
         OGBX_WPATH(20);
 #ifdef OGBX_STAGE_STAMPS
         ss6 += 1;
-        ss7 += it == 0;
+        ss7 += first;
 #endif
 #ifdef OGBX_PHYS_STATS
         if (!done) OGBX_STAT(4);
         trips += !done;
 #endif
         act = A2;
-        piece_weights(act, pw);
+        piece_weights_from(ea, pw);
         local_piece_min(c, pw, vsx, vsy, &ux, &uy);
-        A2 = local_edge_mask(c, ux, uy);
+        A2 = local_edge_mask(c, ux, uy, ea);
         done = A2 == act;
-        if (!__any(!done)) break;
+      };
+      // The first trip in line: most iterating stages settle with it (1.17
+      // trips per iterating stage in the bench states), so they never pay the
+      // rolled loop's counter and exit tests.  At most kLeanIters trips in all.
+      trip(true);
+      if (__any(!done)) {
+#pragma unroll 1
+        for (int it = 1; it < kLeanIters; ++it) {
+          trip(false);
+          if (!__any(!done)) break;
+        }
       }
       bl |= !done;
 #ifdef OGBX_PHYS_STATS

@@ -38,6 +38,16 @@
 using namespace ogbx;
 
 constexpr PointModel kPm = kPointModel;
+
+// Form B keeps the trip loop of the build it was measured against: the piece
+// weights from the integer mask (piece_weights), one rolled kLeanIters loop,
+// hinted cold.  The product's loop (form A) has since moved to the weights
+// from the edge activities and a peeled first trip; B was not kept, so it is
+// not brought along.  The mask alone, for B:
+__device__ __forceinline__ uint32_t local_edge_mask(const LocalSlots& c, double ux, double uy) {
+  EdgeActs e;
+  return local_edge_mask(c, ux, uy, e);
+}
 constexpr int kH = 8, kW = 8;
 
 __global__ void spin_kernel(long long ticks) {

@@ -5,7 +5,9 @@ wave: s_memtime at the kernel's outer boundaries (point_physics.h
 g_path_stamps); consecutive differences are the parts of its stamped lifetime
 (entry to after the final stores), so the parts sum to it.  Reports the
 median band of the contact waves (those that ran the lean loop) and their
-slowest 1 % by lifetime, in s_memtime (shader clock) cycles.
+slowest 1 % by lifetime, in s_memtime (shader clock) cycles, and the shader
+clock itself: delta s_memtime / delta s_memrealtime x 100 MHz, median over the
+contact waves of the last launch of 2 s of back-to-back steps.
 
 Run with OGBX_LIB=_abx/libogbx_path.so built by
   scripts/build_maze_variant.sh path -DOGBX_STAGE_STAMPS=2
@@ -76,6 +78,26 @@ def main():
                                  success_reward=float((tf[:, 8] - tf[:, 3]).mean()),
                                  reset_obs=float((tf[:, 9] - tf[:, 8]).mean()),
                                  final_stores=float((tf[:, 10] - tf[:, 9]).mean()))
+    # shader clock: the -DOGBX_STAGE_STAMPS=2 build takes an s_memrealtime (100 MHz) beside the first and the last
+    # s_memtime stamp (words 11, 12).  Read on the last launch of >= 2 s of back-to-back steps (no synchronize inside).
+    import time
+    torch.cuda.synchronize()
+    _lib.check(L.ogbx_diag_path_stamps(buf))  # clear
+    t0, k = time.perf_counter(), 0
+    while time.perf_counter() - t0 < 2.2:
+        for _ in range(256):
+            env.step(views[k % 128])
+            k += 1
+    torch.cuda.synchronize()
+    _lib.check(L.ogbx_diag_path_stamps(buf))
+    c = np.frombuffer(buf, dtype=np.uint64).reshape(4096, 16)[:nw].astype(np.int64)
+    ok = (c[:, 4] > 0) & (c[:, 6] > 0) & (c[:, 10] > 0) & (c[:, 11] > 0) & (c[:, 12] > c[:, 11])
+    if ok.any():
+        mhz = (c[ok, 10] - c[ok, 0]) / (c[ok, 12] - c[ok, 11]) * 100.0
+        res['shader_clock'] = dict(back_to_back_steps=k, contact_waves=int(ok.sum()), median_mhz=float(np.median(mhz)),
+                                   p10_mhz=float(np.percentile(mhz, 10)), p90_mhz=float(np.percentile(mhz, 90)),
+                                   median_lifetime_ticks=float(np.median(c[ok, 10] - c[ok, 0])),
+                                   median_lifetime_realtime_ticks=float(np.median(c[ok, 12] - c[ok, 11])))
     line = json.dumps(res)
     print(line, flush=True)
     if len(sys.argv) > 2:
