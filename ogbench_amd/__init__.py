@@ -8,15 +8,17 @@ Drop-in for the hot path of hliuson/ogbench:
   * ``datasets.GCDataset``/``HGCDataset`` ~ impls/utils/datasets.py, sampling with
     a fused HIP gather + hindsight-relabel kernel, and ``datasets.ATCDataset``,
     anchor / positive observation pairs for ATC pretraining in one launch, and
-    ``datasets.ReplayBuffer``, batched on-device inserts and uniform sampling.
+    ``datasets.ReplayBuffer``, batched on-device inserts and uniform sampling, and
+    ``datasets.GCReplayBuffer``, hindsight goal sampling over an on-device episode
+    ring filled by the batched envs.
 All compute runs in libogbx.so (HIP, gfx950); there is no CPU fallback.
 """
 
-from .datasets import ATCDataset, Dataset, GCDataset, HGCDataset, ReplayBuffer
+from .datasets import ATCDataset, Dataset, GCDataset, GCReplayBuffer, HGCDataset, ReplayBuffer
 from .locomaze import MazeEnv, parse_env_id
 from .powderworld import PowderworldEnv
 from .registry import make, registered_env_ids
 from .utils import load_dataset, make_env_and_datasets
 
-__all__ = ['ATCDataset', 'Dataset', 'GCDataset', 'HGCDataset', 'MazeEnv', 'PowderworldEnv', 'ReplayBuffer', 'load_dataset', 'make', 'make_env_and_datasets', 'parse_env_id',
+__all__ = ['ATCDataset', 'Dataset', 'GCDataset', 'GCReplayBuffer', 'HGCDataset', 'MazeEnv', 'PowderworldEnv', 'ReplayBuffer', 'load_dataset', 'make', 'make_env_and_datasets', 'parse_env_id',
            'registered_env_ids']

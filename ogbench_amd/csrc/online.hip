@@ -1,0 +1,341 @@
+// online.hip -- hindsight goal sampling over an on-device episode ring on
+// gfx950 (include/ogbx_online.h): one row per env and step kept time-major,
+// episode tables kept at O(1) per inserted row, and GCDataset.sample over the
+// live rows in one launch.
+//
+// Reference (hliuson/ogbench):
+//   GCDataset.sample            impls/utils/datasets.py:213-294
+//   GCDataset.sample_goals      impls/utils/datasets.py:296-327
+// over the snapshot of the ring: the live rows unrolled env-major, flat index
+// u = e * L + k for env e at step S - L + k, a terminal on the last row of
+// every closed episode and on every env's newest row.
+//
+// online_insert_kernel: replay_insert_kernel's tiles and row moves
+// (replay_device.h) without a header or a keep mask: row e of step S goes to
+// row (S % T) * N + e.  The thread of env e also writes ep_seq and, where done,
+// the ep_end entry of the episode it closes and the env's next ordinal; no
+// lane reads what another wrote.
+//
+// online_gc_sample_kernel: gc_sample_kernel's tile structure (gc_device.h) with
+// the index loads replaced by the ring's: the flat pick is split into (e, k),
+// its episode's end comes from ep_seq / cur_seq / ep_end, the goals are drawn
+// on flat indices by sample_goal, and each selector is mapped to its physical
+// row.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "../../include/ogbx_online.h"
+#include "common.h"
+#include "gc_device.h"
+#include "replay_device.h"
+#include "visual_tile.h"
+
+namespace ogbx {
+
+template <int N>
+struct OnlineInsArgs {
+  int64_t n;     // envs
+  int64_t row0;  // (S % T) * N: the first row of this step's slot
+  int64_t step;  // S
+  uint32_t horizon;
+  int32_t tile;  // rows per workgroup, <= kInsRows
+  int32_t* ep_seq;
+  int32_t* cur_seq;
+  int64_t* ep_end;
+  const uint8_t* done;
+  const uint8_t* sel;
+  int32_t num_cols;
+  ogbx_replay_insert_column c[N];
+};
+
+template <int N, bool kNt>
+__global__ void __launch_bounds__(kInsThreads) online_insert_kernel(OnlineInsArgs<N> a) {
+  const int t = threadIdx.x;
+  const int64_t base = (int64_t)blockIdx.x * a.tile;
+  const int n_here = (int)((a.n - base) < a.tile ? (a.n - base) : a.tile);
+  const int64_t row0 = a.row0;
+  // the env's episode tables: tile <= kInsThreads, one env per thread.  Every
+  // index lies below T * N: row0 + e by the host's row0, (seq % T) * N + e by
+  // the modulo, whatever cur_seq holds.
+  if (t < n_here) {
+    const int64_t e = base + t;
+    const uint32_t seq = (uint32_t)a.cur_seq[e];
+    put<kNt>(a.ep_seq + row0 + e, (int32_t)seq);
+    if (a.done[e]) {
+      a.ep_end[(int64_t)(seq % a.horizon) * a.n + e] = a.step;
+      a.cur_seq[e] = (int32_t)(seq + 1u);
+    }
+  }
+  auto slot_of = [row0, base](int b) -> int64_t { return row0 + base + b; };
+  insert_columns<kNt>(a.c, a.num_cols, a.sel, base, n_here, slot_of);
+}
+
+// What the sample kernel needs of the ring, derived on the host from (N, T, S).
+struct OnlineView {
+  const int32_t* ep_seq;
+  const int32_t* cur_seq;
+  const int64_t* ep_end;
+  int64_t n;         // N
+  int64_t live;      // L = min(S, T)
+  int64_t first;     // S - L, the step of k = 0
+  int64_t last;      // S - 1
+  int64_t slot0;     // first % T
+  int64_t horizon;   // T
+  int64_t npick;     // L * N
+  double inv_live;   // 1 / L
+};
+
+// Flat index u in [0, L * N) -> (e, k) with u = e * L + k.  The quotient
+// estimate by the reciprocal is within one of floor(u / L) (u < 2^46 is exact
+// in a double); the remainder test makes it exact (as periodic_row).
+__device__ __forceinline__ void split_flat(const OnlineView& r, int64_t u, int64_t* e, int64_t* k) {
+  int64_t q = (int64_t)((double)u * r.inv_live);
+  int64_t rem = u - q * r.live;
+  if (rem < 0) {
+    --q;
+    rem += r.live;
+  } else if (rem >= r.live) {
+    ++q;
+    rem -= r.live;
+  }
+  *e = q;
+  *k = rem;
+}
+
+// Physical row of env e < N at live offset k < L: slot0 + k < 2 T.
+__device__ __forceinline__ int64_t phys_row(const OnlineView& r, int64_t e, int64_t k) {
+  int64_t s = r.slot0 + k;
+  s = s >= r.horizon ? s - r.horizon : s;
+  return s * r.n + e;
+}
+
+__device__ __forceinline__ int64_t phys_of_flat(const OnlineView& r, int64_t u) {
+  int64_t e, k;
+  split_flat(r, u, &e, &k);
+  return phys_row(r, e, k);
+}
+
+template <bool kInj>
+__global__ void __launch_bounds__(256) online_gc_sample_kernel(
+    OnlineView ring, ogbx_gc_config cfg, GcColumnsSmall cols, int32_t num_cols, int64_t total, int tile,
+    ogbx_gc_draws dr, uint32_t k0, uint32_t k1, uint32_t call_lo, uint32_t call_hi, double v_log_q, double a_log_q,
+    int64_t* idxs_out, int64_t* vgoal_out, int64_t* agoal_out, double* masks, double* rewards,
+    ogbx_gc_draw_record rec, bool flat4) {
+  __shared__ int64_t sel[4][kGcMaxTile];
+  __shared__ uint4 wb[(!kInj && kGcSpread) ? 5 : 1][kGcMaxTile];
+  const int64_t base = xcd_tile() * tile;
+  const int n_here = (int)((total - base) < tile ? (total - base) : tile);
+  if (!kInj && kGcSpread) {
+    tile_philox(wb, 5, n_here, base, call_lo, call_hi, k0, k1);
+    __syncthreads();
+  }
+  // the whole first wave runs the sample chains (lane b % n_here; lanes
+  // b < n_here store): see gc_sample_kernel
+  if (threadIdx.x < 64 && n_here > 0) {
+    const int b = (int)threadIdx.x % n_here;
+    const bool own = (int)threadIdx.x < n_here;
+    const int64_t s = base + b;
+    const uint64_t su = (uint64_t)s;
+    const uint32_t c0 = (uint32_t)su, c3 = (uint32_t)(su >> 32) ^ call_hi;
+    u32x4 w0, w1, w2, w3, w4;
+    if (!kInj && kGcSpread) {
+      w0 = tile_word(wb, 0, b), w1 = tile_word(wb, 1, b), w2 = tile_word(wb, 2, b), w3 = tile_word(wb, 3, b),
+      w4 = tile_word(wb, 4, b);
+    } else {
+      w0 = philox4x32_10({c0, call_lo, 0u, c3}, k0, k1);
+      w1 = philox4x32_10({c0, call_lo, 1u, c3}, k0, k1);
+      w2 = philox4x32_10({c0, call_lo, 2u, c3}, k0, k1);
+      w3 = philox4x32_10({c0, call_lo, 3u, c3}, k0, k1);
+      w4 = philox4x32_10({c0, call_lo, 4u, c3}, k0, k1);
+    }
+    const int64_t npick = ring.npick;
+    // the slot layout of gc_sample_kernel over npick rows without valid_idxs;
+    // injected values are clamped into [0, npick)
+    int64_t idx, pick = -1;
+    if (kInj && dr.idxs) idx = clamp_row(dr.idxs[s], npick);
+    else idx = pick = (kInj && dr.pick) ? clamp_row(dr.pick[s], npick) : (int64_t)bounded64(w0.x, w0.y, (uint64_t)npick);
+    GoalDraws v, a;
+    v.pick = (kInj && dr.v_pick) ? clamp_row(dr.v_pick[s], npick) : (int64_t)bounded64(w0.z, w0.w, (uint64_t)npick);
+    a.pick = (kInj && dr.a_pick) ? clamp_row(dr.a_pick[s], npick) : (int64_t)bounded64(w1.x, w1.y, (uint64_t)npick);
+    // the row's episode: its ordinal and the env's open one load together,
+    // the table entry of a closed episode after them
+    int64_t e, k;
+    split_flat(ring, idx, &e, &k);
+    const int64_t prow = phys_row(ring, e, k);
+    const uint32_t seq = (uint32_t)ring.ep_seq[prow];
+    const uint32_t cur = (uint32_t)ring.cur_seq[e];
+    const int64_t step = ring.first + k;
+    int64_t end = ring.last;  // an open episode ends now
+    if (seq != cur) {
+      end = ring.ep_end[(int64_t)(seq % (uint32_t)ring.horizon) * ring.n + e];
+      end = end < step ? step : (end > ring.last ? ring.last : end);  // whatever the table holds
+    }
+    const int64_t final_idx = idx + (end - step);  // same env: e * L + (end - first)
+    const double uvg = u01_from(w1.z, w1.w), uag = u01_from(w2.x, w2.y);
+    v.geom = (kInj && dr.v_geom) ? dr.v_geom[s] : (cfg.value_geom_sample ? geometric_from(uvg, v_log_q) : 0);
+    a.geom = (kInj && dr.a_geom) ? dr.a_geom[s] : (cfg.actor_geom_sample ? geometric_from(uag, a_log_q) : 0);
+    v.dist = (kInj && dr.v_dist) ? dr.v_dist[s] : uvg;
+    a.dist = (kInj && dr.a_dist) ? dr.a_dist[s] : uag;
+    v.u_traj = (kInj && dr.v_u_traj) ? dr.v_u_traj[s] : u01_from(w2.z, w2.w);
+    v.u_cur = (kInj && dr.v_u_cur) ? dr.v_u_cur[s] : u01_from(w3.x, w3.y);
+    a.u_traj = (kInj && dr.a_u_traj) ? dr.a_u_traj[s] : u01_from(w3.z, w3.w);
+    a.u_cur = (kInj && dr.a_u_cur) ? dr.a_u_cur[s] : u01_from(w4.x, w4.y);
+    int64_t vg = sample_goal(idx, final_idx, v, v.pick, cfg.value_p_curgoal, cfg.value_traj_thresh,
+                             cfg.value_geom_sample, cfg.value_cur_is_one);
+    int64_t ag = sample_goal(idx, final_idx, a, a.pick, cfg.actor_p_curgoal, cfg.actor_traj_thresh,
+                             cfg.actor_geom_sample, cfg.actor_cur_is_one);
+    // in [idx, final_idx] or a pick already; an injected geom / dist may leave
+    vg = clamp_row(vg, npick);
+    ag = clamp_row(ag, npick);
+    const int64_t vrow = phys_of_flat(ring, vg), arow = phys_of_flat(ring, ag);
+    if (own) {
+      sel[0][b] = prow;
+      sel[1][b] = prow;
+      sel[2][b] = vrow;
+      sel[3][b] = arow;
+      if (idxs_out) idxs_out[s] = idx;
+      if (vgoal_out) vgoal_out[s] = vg;
+      if (agoal_out) agoal_out[s] = ag;
+      const double succ = idx == vg ? 1.0 : 0.0;
+      masks[s] = 1.0 - succ;
+      rewards[s] = succ - (cfg.gc_negative ? 1.0 : 0.0);
+      if (rec.pick) {
+        rec.pick[s] = pick;
+        rec.v_pick[s] = v.pick;
+        rec.v_geom[s] = v.geom;
+        rec.v_dist[s] = v.dist;
+        rec.v_u_traj[s] = v.u_traj;
+        rec.v_u_cur[s] = v.u_cur;
+        rec.a_pick[s] = a.pick;
+        rec.a_geom[s] = a.geom;
+        rec.a_dist[s] = a.dist;
+        rec.a_u_traj[s] = a.u_traj;
+        rec.a_u_cur[s] = a.u_cur;
+      }
+    }
+  }
+  __syncthreads();
+  copy_tile<0, false, GcColumnsSmall>(cols, num_cols, sel, base, n_here, flat4);
+}
+
+constexpr int64_t kOnlineMaxRows = (int64_t)1 << 46;  // flat indices stay exact in a double
+
+static ogbx_status check_ring(const ogbx_online_ring* r, const std::string& who) {
+  OGBX_CHECK(r, OGBX_EINVAL, who + "null argument");
+  OGBX_CHECK(r->ep_seq && r->cur_seq && r->ep_end, OGBX_EINVAL, who + "null episode table");
+  OGBX_CHECK(r->num_envs >= 1 && r->num_envs <= 0x7fffffffll, OGBX_EINVAL, who + "num_envs must lie in [1, 2^31)");
+  OGBX_CHECK(r->horizon >= 1 && r->horizon <= 0x7fffffffll, OGBX_EINVAL, who + "horizon must lie in [1, 2^31)");
+  OGBX_CHECK(r->num_envs * r->horizon < kOnlineMaxRows, OGBX_EINVAL, who + "num_envs * horizon must be below 2^46");
+  OGBX_CHECK(r->steps >= 0, OGBX_EINVAL, who + "steps must be >= 0");
+  return OGBX_OK;
+}
+
+template <int N>
+static ogbx_status launch_online_insert(const ogbx_online_ring& r, const ogbx_replay_insert_column* cols,
+                                        int32_t num_cols, const uint8_t* done, const uint8_t* alt_select,
+                                        hipStream_t s) {
+  OnlineInsArgs<N> a{};
+  a.n = r.num_envs;
+  a.row0 = (r.steps % r.horizon) * r.num_envs;
+  a.step = r.steps;
+  a.horizon = (uint32_t)r.horizon;
+  a.ep_seq = r.ep_seq;
+  a.cur_seq = r.cur_seq;
+  a.ep_end = r.ep_end;
+  a.done = done;
+  a.sel = alt_select;
+  a.num_cols = num_cols;
+  for (int i = 0; i < num_cols; ++i) a.c[i] = cols[i];
+  // the rows per workgroup of replay_insert_kernel (the 4 B of ep_seq per row not counted)
+  a.tile = insert_tile(cols, num_cols, r.num_envs);
+  const int64_t blocks = (r.num_envs + a.tile - 1) / a.tile;
+  hipLaunchKernelGGL((online_insert_kernel<N, kInsNt>), dim3((uint32_t)blocks), dim3(kInsThreads), 0, s, a);
+  OGBX_LAUNCHED("online_insert_kernel");
+  return OGBX_OK;
+}
+
+}  // namespace ogbx
+
+using namespace ogbx;
+
+extern "C" {
+
+int32_t ogbx_online_api_version(void) { return OGBX_ONLINE_API_VERSION; }
+
+ogbx_status ogbx_online_insert(const ogbx_online_ring* ring, const ogbx_replay_insert_column* cols,
+                               int32_t num_cols, const uint8_t* done, const uint8_t* alt_select, void* stream) {
+  const std::string who = "ogbx_online_insert: ";
+  if (ogbx_status st = check_ring(ring, who)) return st;
+  OGBX_CHECK(done, OGBX_EINVAL, who + "null done");
+  OGBX_CHECK(num_cols >= 0 && num_cols <= OGBX_REPLAY_MAX_COLS, OGBX_EINVAL, who + "0 to 16 columns");
+  OGBX_CHECK(num_cols == 0 || cols, OGBX_EINVAL, who + "null columns");
+  if (ogbx_status st = check_insert_columns(cols, num_cols, alt_select, who)) return st;
+  hipStream_t s = (hipStream_t)stream;
+  // the kernel arguments grow the host's launch cost (gc_device.h kGcSmallCols)
+  if (num_cols <= 8) return launch_online_insert<8>(*ring, cols, num_cols, done, alt_select, s);
+  return launch_online_insert<16>(*ring, cols, num_cols, done, alt_select, s);
+}
+
+ogbx_status ogbx_online_clear(const ogbx_online_ring* ring, void* stream) {
+  const std::string who = "ogbx_online_clear: ";
+  if (ogbx_status st = check_ring(ring, who)) return st;
+  OGBX_HIP(hipMemsetAsync(ring->cur_seq, 0, (size_t)ring->num_envs * sizeof(int32_t), (hipStream_t)stream));
+  return OGBX_OK;
+}
+
+ogbx_status ogbx_online_gc_sample(const ogbx_online_ring* ring, const ogbx_gc_config* cfg,
+                                  const ogbx_online_batch* batch, const ogbx_gc_draws* draws,
+                                  const ogbx_gc_draw_record* record, uint64_t seed, uint64_t call_index,
+                                  void* stream) {
+  const std::string who = "ogbx_online_gc_sample: ";
+  if (ogbx_status st = check_ring(ring, who)) return st;
+  OGBX_CHECK(cfg && batch, OGBX_EINVAL, who + "null argument");
+  OGBX_CHECK(ring->steps >= 1, OGBX_EINVAL, who + "the ring is empty (steps must be >= 1)");
+  OGBX_CHECK(batch->masks && batch->rewards, OGBX_EINVAL, who + "null masks / rewards");
+  OGBX_CHECK(batch->total > 0, OGBX_EINVAL, who + "total must be > 0");
+  const int32_t num_cols = batch->num_cols;
+  OGBX_CHECK(num_cols >= 0 && num_cols <= OGBX_REPLAY_MAX_COLS, OGBX_EINVAL, who + "0 to 16 columns");
+  OGBX_CHECK(num_cols == 0 || batch->cols, OGBX_EINVAL, who + "null columns");
+  GcColumnsSmall cc{};
+  bool flat4 = true;
+  for (int i = 0; i < num_cols; ++i) {
+    const ogbx_gc_column& c = batch->cols[i];
+    OGBX_CHECK(c.src && c.dst, OGBX_EINVAL, who + "null column pointer");
+    OGBX_CHECK(c.row_bytes > 0 && (c.select == 0 || c.select == 2 || c.select == 3), OGBX_EINVAL,
+               who + "bad column descriptor");
+    OGBX_CHECK(c.src_stride == 0 || c.src_stride >= c.row_bytes, OGBX_EINVAL, who + "src_stride below row_bytes");
+    cc.c[i] = c;
+    // copy_tile's per-wave job copy: 4-byte granular, aligned rows of <= 128 words
+    flat4 = flat4 && c.row_bytes % 4 == 0 && c.row_bytes <= 512 &&
+            ((uintptr_t)c.src | (uintptr_t)c.dst | (uintptr_t)c.src_stride) % 4 == 0;
+  }
+  const int64_t total = batch->total;
+  const int64_t tile = gc_tile(total);
+  const int64_t blocks = (total + tile - 1) / tile;
+  OGBX_CHECK(blocks <= 0x7fffffffll, OGBX_EINVAL, who + "too many samples for one launch");
+
+  OnlineView v{};
+  v.ep_seq = ring->ep_seq;
+  v.cur_seq = ring->cur_seq;
+  v.ep_end = ring->ep_end;
+  v.n = ring->num_envs;
+  v.horizon = ring->horizon;
+  v.live = std::min(ring->steps, ring->horizon);
+  v.first = ring->steps - v.live;
+  v.last = ring->steps - 1;
+  v.slot0 = v.first % v.horizon;
+  v.npick = v.live * v.n;
+  v.inv_live = 1.0 / (double)v.live;
+  const ogbx_gc_draws dr = draws ? *draws : ogbx_gc_draws{};
+  const GcParams pr = gc_params(seed, *cfg, nullptr);
+  const auto kern = any_draw(dr) ? online_gc_sample_kernel<true> : online_gc_sample_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, v, *cfg, cc, num_cols, total,
+                     (int)tile, dr, pr.k0, pr.k1, (uint32_t)call_index, (uint32_t)(call_index >> 32), pr.v_log_q,
+                     pr.a_log_q, batch->idxs_out, batch->value_goal_out, batch->actor_goal_out, batch->masks,
+                     batch->rewards, record ? *record : ogbx_gc_draw_record{}, flat4 && tile <= 4);
+  OGBX_LAUNCHED("online_gc_sample_kernel");
+  return OGBX_OK;
+}
+
+}  // extern "C"

@@ -19,6 +19,11 @@ Batched, device-side counterparts of impls/utils/datasets.py (hliuson/ogbench):
                and ``sample`` over the rows held so far; ``add_transitions`` /
                ``add_step`` insert one row per env in one launch of
                ``replay_insert_kernel`` (include/ogbx_replay.h).
+  GCReplayBuffer  GCDataset.sample over a growing buffer: a time-major
+               episode ring filled one row per env and step
+               (``online_insert_kernel``) and sampled as the reference samples
+               the snapshot of its live rows (``online_gc_sample_kernel``,
+               include/ogbx_online.h).
 
 Every sample is ONE launch of ``gc_sample_kernel`` (libogbx): index draw,
 trajectory-end lookup, hindsight goal relabel and the row gathers of every
@@ -216,6 +221,33 @@ REPLAY_MAX_COLS = 16  # OGBX_REPLAY_MAX_COLS
 REPLAY_OP_NONE, REPLAY_OP_ONE_MINUS = 0, 1  # ogbx_replay_op
 
 
+class OnlineRing(ctypes.Structure):
+    """ogbx_online_ring (include/ogbx_online.h)."""
+    _fields_ = [
+        ('num_envs', ctypes.c_int64),
+        ('horizon', ctypes.c_int64),
+        ('steps', ctypes.c_int64),
+        ('ep_seq', ctypes.c_void_p),
+        ('cur_seq', ctypes.c_void_p),
+        ('ep_end', ctypes.c_void_p),
+    ]
+
+
+class OnlineBatch(ctypes.Structure):
+    """ogbx_online_batch (include/ogbx_online.h)."""
+    _fields_ = [
+        ('cols', ctypes.c_void_p),
+        ('num_cols', ctypes.c_int32),
+        ('pad_', ctypes.c_int32),
+        ('total', ctypes.c_int64),
+        ('idxs_out', ctypes.c_void_p),
+        ('value_goal_out', ctypes.c_void_p),
+        ('actor_goal_out', ctypes.c_void_p),
+        ('masks', ctypes.c_void_p),
+        ('rewards', ctypes.c_void_p),
+    ]
+
+
 def _bind():
     L = _lib.lib()
     if not getattr(L, '_gc_bound', False):
@@ -297,6 +329,17 @@ def _bind():
         L.ogbx_replay_sample.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
                                          ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint64,
                                          ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        # include/ogbx_online.h (likewise)
+        L.ogbx_online_api_version.restype = ctypes.c_int32
+        L.ogbx_online_api_version.argtypes = []
+        L.ogbx_online_insert.restype = ctypes.c_int32
+        L.ogbx_online_insert.argtypes = [P(OnlineRing), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p]
+        L.ogbx_online_clear.restype = ctypes.c_int32
+        L.ogbx_online_clear.argtypes = [P(OnlineRing), ctypes.c_void_p]
+        L.ogbx_online_gc_sample.restype = ctypes.c_int32
+        L.ogbx_online_gc_sample.argtypes = [P(OnlineRing), P(GcConfig), P(OnlineBatch), P(GcDraws), P(GcDrawRecord),
+                                            ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
         L._gc_bound = True
     return L
 
@@ -422,6 +465,20 @@ _PLAIN_CONFIG = dict(
     actor_p_curgoal=1.0, actor_p_trajgoal=0.0, actor_p_randomgoal=0.0, actor_geom_sample=False,
     gc_negative=False, p_aug=None, frame_stack=None,
 )
+
+
+def _gc_config(c):
+    """ogbx_gc_config of a GCDataset config dict."""
+
+    def thresh(p_traj, p_cur):
+        return p_traj / (1.0 - p_cur) if p_cur != 1.0 else 0.0  # datasets.py:321
+
+    return GcConfig(
+        float(c['value_p_curgoal']), thresh(c['value_p_trajgoal'], c['value_p_curgoal']), float(c['discount']),
+        float(c['actor_p_curgoal']), thresh(c['actor_p_trajgoal'], c['actor_p_curgoal']), float(c['discount']),
+        int(bool(c['value_geom_sample'])), int(bool(c['actor_geom_sample'])),
+        int(c['value_p_curgoal'] == 1.0), int(c['actor_p_curgoal'] == 1.0), int(bool(c['gc_negative'])), 0,
+    )
 
 
 class GCDataset:
@@ -590,16 +647,7 @@ class GCDataset:
         # its generation and (_rec_versions) the packed columns' versions
         self._tok_ds, self._tok_gen = dataset, dataset._gen
 
-        def thresh(p_traj, p_cur):
-            return p_traj / (1.0 - p_cur) if p_cur != 1.0 else 0.0  # datasets.py:321
-
-        c = config
-        self._cfg = GcConfig(
-            float(c['value_p_curgoal']), thresh(c['value_p_trajgoal'], c['value_p_curgoal']), float(c['discount']),
-            float(c['actor_p_curgoal']), thresh(c['actor_p_trajgoal'], c['actor_p_curgoal']), float(c['discount']),
-            int(bool(c['value_geom_sample'])), int(bool(c['actor_geom_sample'])),
-            int(c['value_p_curgoal'] == 1.0), int(c['actor_p_curgoal'] == 1.0), int(bool(c['gc_negative'])), 0,
-        )
+        self._cfg = _gc_config(config)
         self._seed = int(seed) if seed is not None else None
         self._calls = 0
         self._out_cache = {}
@@ -2006,3 +2054,330 @@ class ReplayBuffer(Dataset):
     def get_random_idxs(self, num_idxs):
         """Uniform rows of ``[0, size)`` (datasets.py:65-70)."""
         return self.sample(num_idxs, record_idxs=True)['_idxs']
+
+
+class GCReplayBuffer(Dataset):
+    """Hindsight goal sampling over an on-device episode ring: what batched
+    envs produce, one row per env and step, sampled as the reference's
+    ``GCDataset.sample`` (datasets.py:213-327) samples a dataset
+    (include/ogbx_online.h).
+
+    Layout.  ``num_envs = N`` lanes and ``horizon = T`` time slots; every
+    insert takes exactly one row from every env, and the row of env e at
+    logical step t lives at physical row ``(t % T) * N + e`` of every column
+    (``[T * N, *shape]``).  The host counts the steps ``S`` (``steps``);
+    ``L = min(S, T)`` of them are live (``live_steps``), ``S - L .. S - 1``.
+    ``done[e]`` (terminated | truncated of an auto-reset env) closes env e's
+    episode at that step.
+
+    The snapshot (``snapshot()``) is the dataset of the live rows unrolled
+    env-major -- flat index ``u = e * L + k`` holds env e at step
+    ``S - L + k`` -- with ``terminals = 1`` on the last row of every closed
+    episode and on every env's newest row (an open episode ends "now").  An
+    episode whose head was overwritten starts at its oldest live row.
+    ``sample`` returns, bit for bit, what ``GCDataset(Dataset(snapshot),
+    config).sample`` returns under the same draws, for every key of the
+    buffer, ``value_goals`` / ``actor_goals`` (from ``oracle_reps`` when the
+    buffer has that column, else ``observations``), ``masks`` and ``rewards``;
+    with the Philox draws at one ``(seed, call)`` too.  Every index it takes or
+    reports (``idxs``, the draws' picks, ``_idxs`` and the goal indices of a
+    recording call) is a flat index of the snapshot.  A ``terminals`` column of
+    the buffer holds what was inserted (``add_step``: done); the snapshot's
+    ``terminals`` also marks the newest rows.
+
+    ``add`` / ``add_step`` are ONE launch of ``online_insert_kernel``, which
+    also keeps the episode tables at O(1) per row (``ep_seq``, ``cur_seq``,
+    ``ep_end``); ``sample`` is ONE launch of ``online_gc_sample_kernel``.
+    Nothing is read back.  The regular layout only: the buffer stores its own
+    ``next_observations``; no ``valids``, no ``frame_stack``.
+    """
+
+    RESERVED = ('masks', 'rewards', 'value_goals', 'actor_goals', 'valids')
+    STEP_KEYS = ('observations', 'actions', 'next_observations', 'terminals')
+
+    @classmethod
+    def create(cls, transition, num_envs, horizon, config, device=None, seed=None):
+        """Zero columns ``[horizon * num_envs, *shape]`` with the dtype of
+        ``np.array(example)``, as ``ReplayBuffer.create``."""
+        torch = _torch()
+        if device is None:
+            device = 'cuda'
+        num_envs, horizon = operator.index(num_envs), operator.index(horizon)
+        if num_envs <= 0 or horizon <= 0:
+            raise ValueError(f'num_envs and horizon must be > 0, got {num_envs} and {horizon}')
+        cols = {}
+        for k, example in transition.items():
+            if isinstance(example, torch.Tensor):
+                shape, dtype = tuple(example.shape), example.dtype
+            else:
+                example = np.array(example)
+                shape, dtype = example.shape, torch.from_numpy(np.zeros(0, example.dtype)).dtype
+            cols[k] = torch.zeros((horizon * num_envs,) + tuple(shape), dtype=dtype, device=device)
+        return cls(cols, num_envs, horizon, config, device=device, seed=seed)
+
+    def __init__(self, data, num_envs, horizon, config, device=None, seed=None):
+        torch = _torch()
+        data = dict(data)
+        bad = [k for k in data if k in self.RESERVED]
+        if bad:
+            raise ValueError(f'a GCReplayBuffer cannot have columns named {bad}: sample() returns keys of these names')
+        if 'observations' not in data:
+            raise ValueError("a GCReplayBuffer needs an 'observations' column")
+        self._steps = None
+        super().__init__(data, device=device)
+        self.num_envs, self.horizon = operator.index(num_envs), operator.index(horizon)
+        if self.num_envs <= 0 or self.horizon <= 0:
+            raise ValueError(f'num_envs and horizon must be > 0, got {num_envs} and {horizon}')
+        self.rows = self.num_envs * self.horizon
+        if {len(v) for v in self.values()} != {self.rows}:
+            raise ValueError(f'every column of a GCReplayBuffer needs horizon * num_envs = {self.rows} rows')
+        if len(self) + 2 > REPLAY_MAX_COLS:
+            raise ValueError(f'at most {REPLAY_MAX_COLS - 2} columns (a batch adds the two goal columns)')
+        self.config = config
+        assert np.isclose(config['value_p_curgoal'] + config['value_p_trajgoal'] + config['value_p_randomgoal'], 1.0)
+        assert np.isclose(config['actor_p_curgoal'] + config['actor_p_trajgoal'] + config['actor_p_randomgoal'], 1.0)
+        self._cfg = _gc_config(config)
+        self._L = _bind()
+        self._dtype_code = _replay_dtypes()
+        self.ep_seq = torch.zeros(self.horizon, self.num_envs, dtype=torch.int32, device=self.device)
+        self.cur_seq = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        self.ep_end = torch.zeros(self.horizon, self.num_envs, dtype=torch.int64, device=self.device)
+        self._ring = OnlineRing(self.num_envs, self.horizon, 0, self.ep_seq.data_ptr(), self.cur_seq.data_ptr(),
+                                self.ep_end.data_ptr())
+        self._done = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)  # add_step's terminated | truncated
+        self._steps = 0
+        self._seed = int(seed) if seed is not None else None
+        self._calls = 0
+        self._ins_cache = {}
+        self._out_cache = {}
+        self._out_gen = self._gen
+        self._dev_idx = self.device.index
+        self._raw_stream = torch._C._cuda_getCurrentRawStream  # hipStream_t of the current stream, as an int
+
+    _next_seed = GCDataset._next_seed
+    _source = ReplayBuffer._source
+    _mask = ReplayBuffer._mask
+    _check_keys = ReplayBuffer._check_keys
+
+    # ------------------------------------------------------------------- state
+    @property
+    def steps(self):
+        """S: the steps inserted since creation or ``clear()``."""
+        return self._steps
+
+    @property
+    def live_steps(self):
+        """L = min(S, T)."""
+        return min(self._steps, self.horizon)
+
+    @property
+    def size(self):
+        """Rows of the snapshot, L * N."""
+        return self.live_steps * self.num_envs
+
+    @size.setter
+    def size(self, value):  # Dataset.__init__'s row count
+        pass
+
+    def clear(self):
+        """S = 0 and every env's episode ordinal back to 0, on the stream; the
+        rows stay where they are."""
+        _lib.check(self._L.ogbx_online_clear(self._ring, _lib.stream_of(self.device)), 'online_clear')
+        self._steps = self._ring.steps = 0
+
+    # ------------------------------------------------------------------ inserts
+    def _insert(self, specs, done, alt_select):
+        """specs: (key, src, alt or None, op) per column, staged by
+        ``_source``.  One launch; then S + 1."""
+        key = (done.data_ptr(), alt_select.data_ptr() if alt_select is not None else 0, self._gen) + tuple(
+            (k, s.data_ptr(), s.dtype, a.data_ptr() if a is not None else 0, op) for k, s, a, op in specs)
+        arr = self._ins_cache.get(key)
+        if arr is None:
+            code = self._dtype_code
+            cols = []
+            for k, s, a, op in specs:
+                col = self[k]
+                if len(col) != self.rows or not col.is_contiguous() or col.device != self.device:
+                    raise ValueError(f'buffer column {k!r} was replaced by one of another length, layout or device')
+                if col.dtype not in code or col.dtype is _torch().bool:
+                    raise ValueError(f'{k!r}: unsupported column dtype {col.dtype}')
+                if a is not None and a.dtype != s.dtype:
+                    raise ValueError(f'{k!r}: the alternative source has dtype {a.dtype}, the source {s.dtype}')
+                row = col[0].numel() if col.dim() > 1 else 1
+                cols.append(ReplayInsertColumn(col.data_ptr(), s.data_ptr(), a.data_ptr() if a is not None else None,
+                                               row, code[s.dtype], code[col.dtype], op, 0))
+            arr = (ReplayInsertColumn * len(cols))(*cols)
+            if len(self._ins_cache) >= 8:
+                self._ins_cache.clear()
+            self._ins_cache[key] = arr
+        st = self._L.ogbx_online_insert(self._ring, arr, len(arr), done.data_ptr(),
+                                        alt_select.data_ptr() if alt_select is not None else None,
+                                        self._raw_stream(self._dev_idx))
+        if st:
+            _lib.check(st, 'online_insert')
+        self._steps += 1
+        self._ring.steps = self._steps
+
+    def add(self, batch, done):
+        """Insert one step: every leaf of ``batch`` has a leading N and
+        ``done`` is bool / uint8 ``[N]``.  A wrong N, keys that differ from the
+        buffer's or a leaf of another shape raise ValueError."""
+        self._check_keys(batch)
+        n = self.num_envs
+        specs = [(k, self._source(k, batch[k], n), None, REPLAY_OP_NONE) for k in self]
+        self._insert(specs, self._mask('done', done, n), None)
+
+    def add_step(self, observations, actions, terminated, truncated, next_observations, final_observation=None):
+        """Insert what a vectorized env's ``step`` returned in one launch:
+        ``observations``, ``actions``, ``next_observations`` -- taken from
+        ``final_observation`` (``info['final_observation']`` of an
+        ``auto_reset=True`` env) where done = terminated | truncated -- and
+        ``terminals`` = done as float32.  The buffer's keys must be
+        ``STEP_KEYS``.  ``truncated=None`` takes ``terminated`` as done;
+        otherwise the two masks are combined by one elementwise op before the
+        launch.
+
+        ``observations`` must be a tensor the caller still owns: the env's
+        observation view is overwritten by the step that produced
+        ``next_observations``, so pass a copy taken before that step."""
+        torch = _torch()
+        self._check_keys(self.STEP_KEYS)
+        n = self.num_envs
+        done = self._mask('terminated', terminated, n)
+        if truncated is not None:
+            done = torch.logical_or(done, self._mask('truncated', truncated, n), out=self._done)
+        src = dict(observations=observations, actions=actions, next_observations=next_observations, terminals=done)
+        alt = self._source('next_observations', final_observation, n) if final_observation is not None else None
+        specs = [(k, self._source(k, src[k], n), alt if k == 'next_observations' else None, REPLAY_OP_NONE)
+                 for k in self]
+        self._insert(specs, done, done if alt is not None else None)
+
+    # ----------------------------------------------------------------- sampling
+    def _batch(self, B, record):
+        torch = _torch()
+        out, cols = {}, []
+
+        def add(src_key, dst_key, select):
+            src = self[src_key]
+            if len(src) != self.rows or not src.is_contiguous() or src.device != self.device:
+                raise ValueError(f'buffer column {src_key!r} was replaced by one of another length, layout or device')
+            dst = torch.empty((B,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
+            out[dst_key] = dst
+            row_bytes = (src[0].numel() if src.dim() > 1 else 1) * src.element_size()
+            cols.append(GcColumn(src.data_ptr(), dst.data_ptr(), row_bytes, select, 0))
+
+        for k in self.keys():
+            add(k, k, 0)
+        goal_src = 'oracle_reps' if 'oracle_reps' in self else 'observations'  # datasets.py:348-357
+        add(goal_src, 'value_goals', 2)
+        add(goal_src, 'actor_goals', 3)
+        if len(cols) > REPLAY_MAX_COLS:
+            raise ValueError(f'at most {REPLAY_MAX_COLS} columns per sample, got {len(cols)}')
+        out['masks'] = torch.empty(B, dtype=torch.float64, device=self.device)
+        out['rewards'] = torch.empty(B, dtype=torch.float64, device=self.device)
+        idx_t = {}
+        if record:
+            idx_t = {k: torch.empty(B, dtype=torch.int64, device=self.device)
+                     for k in ('_idxs', '_value_goal_idxs', '_actor_goal_idxs')}
+        arr = (GcColumn * len(cols))(*cols)
+        batch = OnlineBatch(ctypes.cast(arr, ctypes.c_void_p), len(cols), 0, B,
+                            *[t.data_ptr() for t in idx_t.values()] if record else (None, None, None),
+                            out['masks'].data_ptr(), out['rewards'].data_ptr())
+        return out, (batch, arr), idx_t
+
+    def sample(self, batch_size, idxs=None, draws=None, record_draws=False, out=None):
+        """GCDataset.sample (datasets.py:213-294) over the snapshot, one
+        launch.  Raises ValueError while no step was inserted.
+
+        idxs: explicit flat rows of the snapshot, clamped into ``[0, L * N)``.
+        draws: injected reference draws (``_DRAW_ORDER``), picks as flat rows.
+        record_draws: also return the draws used (``out['_draws']``) and the
+        flat ``_idxs`` / ``_value_goal_idxs`` / ``_actor_goal_idxs``.
+        out: a batch returned by an earlier plain call with the same
+        batch_size: refilled in place, stream ordered, and returned (a batch
+        of another size raises ValueError).
+        """
+        torch = _torch()
+        B = int(batch_size)
+        if self._steps == 0:
+            raise ValueError('cannot sample from an empty GCReplayBuffer')
+        plain = idxs is None and not draws and not record_draws
+        if self._out_gen != self._gen:  # a column was replaced
+            self._out_cache.clear()
+            self._out_gen = self._gen
+        hit = self._out_cache.get(id(out)) if (out is not None and plain) else None
+        if hit is not None and hit[0] is out and hit[1] == B:
+            call = self._calls
+            self._calls = call + 1
+            st = self._L.ogbx_online_gc_sample(self._ring, self._cfg, hit[2][0], None, None, self._seed, call,
+                                               self._raw_stream(self._dev_idx))
+            if st:
+                _lib.check(st, 'online_gc_sample')
+            return out
+        if out is not None and len(out['masks']) != B:
+            raise ValueError(f"out= holds a batch of {len(out['masks'])} samples, not {B}")
+        out, held, idx_t = self._batch(B, record_draws)
+        dr = rec = rec_t = None
+        staged = []
+        if idxs is not None or draws:
+            dr = GcDraws()
+            if idxs is not None:
+                t = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
+                if t.numel() != B:
+                    raise ValueError(f'idxs must have {B} entries, got {t.numel()}')
+                staged.append(t)
+                dr.idxs = t.data_ptr()
+            for k, v in (draws or {}).items():
+                if k == 'idxs':
+                    continue
+                if k not in _DRAW_ORDER:
+                    raise ValueError(f'unknown draw {k!r}')
+                t = _to_device(v, self.device).to(torch.int64 if k in _DRAW_INT else torch.float64).reshape(-1)
+                if t.numel() != B:
+                    raise ValueError(f'draw {k!r} must have {B} entries, got {t.numel()}')
+                staged.append(t)
+                setattr(dr, k, t.data_ptr())
+        if record_draws:
+            rec_t = {k: torch.empty(B, dtype=torch.int64 if k in _DRAW_INT else torch.float64, device=self.device)
+                     for k in _DRAW_ORDER}
+            rec = GcDrawRecord(*[rec_t[k].data_ptr() for k in _DRAW_ORDER])
+        seed, call = self._next_seed()
+        st = self._L.ogbx_online_gc_sample(self._ring, self._cfg, held[0], dr, rec, seed, call,
+                                           self._raw_stream(self._dev_idx))
+        _lib.check(st, 'online_gc_sample')
+        del staged  # alive until the launch was issued
+        if plain:
+            if len(self._out_cache) >= 2:
+                self._out_cache.clear()
+            self._out_cache[id(out)] = (out, B, held)
+        if record_draws:
+            out['_draws'] = rec_t
+            out.update(idx_t)
+        return out
+
+    def get_subset(self, idxs):
+        return self.sample(len(idxs), idxs=idxs)
+
+    def get_random_idxs(self, num_idxs):
+        """Uniform flat rows of the snapshot."""
+        return self.sample(num_idxs, record_draws=True)['_idxs']
+
+    # ----------------------------------------------------------------- snapshot
+    def snapshot(self):
+        """The live rows as a ``Dataset`` in the OGBench layout: every column
+        unrolled env-major (row ``e * L + k`` = env e at step ``S - L + k``)
+        plus ``terminals`` (float32): 1 on the last row of every closed episode
+        and on every env's newest row.  Built with torch ops (not a hot path):
+        for tests, and for saving collected data."""
+        torch = _torch()
+        S, T, N, L = self._steps, self.horizon, self.num_envs, self.live_steps
+        if S == 0:
+            raise ValueError('an empty GCReplayBuffer has no snapshot')
+        slots = torch.arange(S - L, S, dtype=torch.int64, device=self.device) % T  # [L]
+        rows = (slots[None, :] * N + torch.arange(N, dtype=torch.int64, device=self.device)[:, None]).reshape(-1)
+        data = {k: v.index_select(0, rows) for k, v in self.items()}
+        seq = self.ep_seq.reshape(-1).index_select(0, rows).reshape(N, L)
+        term = torch.ones(N, L, dtype=torch.float32, device=self.device)
+        term[:, :-1] = (seq[:, 1:] != seq[:, :-1]).to(torch.float32)  # the next live row belongs to another episode
+        data['terminals'] = term.reshape(-1)
+        return Dataset(data, device=self.device)
