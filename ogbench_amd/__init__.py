@@ -10,15 +10,16 @@ Drop-in for the hot path of hliuson/ogbench:
     anchor / positive observation pairs for ATC pretraining in one launch, and
     ``datasets.ReplayBuffer``, batched on-device inserts and uniform sampling, and
     ``datasets.GCReplayBuffer``, hindsight goal sampling over an on-device episode
-    ring filled by the batched envs.
+    ring filled by the batched envs, and ``datasets.HGCReplayBuffer``, the
+    hierarchical (HIQL) batch over the same ring.
 All compute runs in libogbx.so (HIP, gfx950); there is no CPU fallback.
 """
 
-from .datasets import ATCDataset, Dataset, GCDataset, GCReplayBuffer, HGCDataset, ReplayBuffer
+from .datasets import ATCDataset, Dataset, GCDataset, GCReplayBuffer, HGCDataset, HGCReplayBuffer, ReplayBuffer
 from .locomaze import MazeEnv, parse_env_id
 from .powderworld import PowderworldEnv
 from .registry import make, registered_env_ids
 from .utils import load_dataset, make_env_and_datasets
 
-__all__ = ['ATCDataset', 'Dataset', 'GCDataset', 'GCReplayBuffer', 'HGCDataset', 'MazeEnv', 'PowderworldEnv', 'ReplayBuffer', 'load_dataset', 'make', 'make_env_and_datasets', 'parse_env_id',
+__all__ = ['ATCDataset', 'Dataset', 'GCDataset', 'GCReplayBuffer', 'HGCDataset', 'HGCReplayBuffer', 'MazeEnv', 'PowderworldEnv', 'ReplayBuffer', 'load_dataset', 'make', 'make_env_and_datasets', 'parse_env_id',
            'registered_env_ids']

@@ -20,7 +20,8 @@
 // the index loads replaced by the ring's: the flat pick is split into (e, k),
 // its episode's end comes from ep_seq / cur_seq / ep_end, the goals are drawn
 // on flat indices by sample_goal, and each selector is mapped to its physical
-// row.
+// row.  The ring's view, the row map and the end lookup live in
+// online_device.h, shared with online_hgc_sample_kernel (online_hgc.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +29,7 @@
 #include "../../include/ogbx_online.h"
 #include "common.h"
 #include "gc_device.h"
+#include "online_device.h"
 #include "replay_device.h"
 #include "visual_tile.h"
 
@@ -69,51 +71,6 @@ __global__ void __launch_bounds__(kInsThreads) online_insert_kernel(OnlineInsArg
   }
   auto slot_of = [row0, base](int b) -> int64_t { return row0 + base + b; };
   insert_columns<kNt>(a.c, a.num_cols, a.sel, base, n_here, slot_of);
-}
-
-// What the sample kernel needs of the ring, derived on the host from (N, T, S).
-struct OnlineView {
-  const int32_t* ep_seq;
-  const int32_t* cur_seq;
-  const int64_t* ep_end;
-  int64_t n;         // N
-  int64_t live;      // L = min(S, T)
-  int64_t first;     // S - L, the step of k = 0
-  int64_t last;      // S - 1
-  int64_t slot0;     // first % T
-  int64_t horizon;   // T
-  int64_t npick;     // L * N
-  double inv_live;   // 1 / L
-};
-
-// Flat index u in [0, L * N) -> (e, k) with u = e * L + k.  The quotient
-// estimate by the reciprocal is within one of floor(u / L) (u < 2^46 is exact
-// in a double); the remainder test makes it exact (as periodic_row).
-__device__ __forceinline__ void split_flat(const OnlineView& r, int64_t u, int64_t* e, int64_t* k) {
-  int64_t q = (int64_t)((double)u * r.inv_live);
-  int64_t rem = u - q * r.live;
-  if (rem < 0) {
-    --q;
-    rem += r.live;
-  } else if (rem >= r.live) {
-    ++q;
-    rem -= r.live;
-  }
-  *e = q;
-  *k = rem;
-}
-
-// Physical row of env e < N at live offset k < L: slot0 + k < 2 T.
-__device__ __forceinline__ int64_t phys_row(const OnlineView& r, int64_t e, int64_t k) {
-  int64_t s = r.slot0 + k;
-  s = s >= r.horizon ? s - r.horizon : s;
-  return s * r.n + e;
-}
-
-__device__ __forceinline__ int64_t phys_of_flat(const OnlineView& r, int64_t u) {
-  int64_t e, k;
-  split_flat(r, u, &e, &k);
-  return phys_row(r, e, k);
 }
 
 template <bool kInj>
@@ -158,20 +115,11 @@ __global__ void __launch_bounds__(256) online_gc_sample_kernel(
     GoalDraws v, a;
     v.pick = (kInj && dr.v_pick) ? clamp_row(dr.v_pick[s], npick) : (int64_t)bounded64(w0.z, w0.w, (uint64_t)npick);
     a.pick = (kInj && dr.a_pick) ? clamp_row(dr.a_pick[s], npick) : (int64_t)bounded64(w1.x, w1.y, (uint64_t)npick);
-    // the row's episode: its ordinal and the env's open one load together,
-    // the table entry of a closed episode after them
+    // the row's episode end (online_device.h): ep_seq / cur_seq, then ep_end
     int64_t e, k;
     split_flat(ring, idx, &e, &k);
     const int64_t prow = phys_row(ring, e, k);
-    const uint32_t seq = (uint32_t)ring.ep_seq[prow];
-    const uint32_t cur = (uint32_t)ring.cur_seq[e];
-    const int64_t step = ring.first + k;
-    int64_t end = ring.last;  // an open episode ends now
-    if (seq != cur) {
-      end = ring.ep_end[(int64_t)(seq % (uint32_t)ring.horizon) * ring.n + e];
-      end = end < step ? step : (end > ring.last ? ring.last : end);  // whatever the table holds
-    }
-    const int64_t final_idx = idx + (end - step);  // same env: e * L + (end - first)
+    const int64_t final_idx = episode_end_flat(ring, episode_seq(ring, e, prow), idx, e, k);
     const double uvg = u01_from(w1.z, w1.w), uag = u01_from(w2.x, w2.y);
     v.geom = (kInj && dr.v_geom) ? dr.v_geom[s] : (cfg.value_geom_sample ? geometric_from(uvg, v_log_q) : 0);
     a.geom = (kInj && dr.a_geom) ? dr.a_geom[s] : (cfg.actor_geom_sample ? geometric_from(uag, a_log_q) : 0);
@@ -217,18 +165,6 @@ __global__ void __launch_bounds__(256) online_gc_sample_kernel(
   }
   __syncthreads();
   copy_tile<0, false, GcColumnsSmall>(cols, num_cols, sel, base, n_here, flat4);
-}
-
-constexpr int64_t kOnlineMaxRows = (int64_t)1 << 46;  // flat indices stay exact in a double
-
-static ogbx_status check_ring(const ogbx_online_ring* r, const std::string& who) {
-  OGBX_CHECK(r, OGBX_EINVAL, who + "null argument");
-  OGBX_CHECK(r->ep_seq && r->cur_seq && r->ep_end, OGBX_EINVAL, who + "null episode table");
-  OGBX_CHECK(r->num_envs >= 1 && r->num_envs <= 0x7fffffffll, OGBX_EINVAL, who + "num_envs must lie in [1, 2^31)");
-  OGBX_CHECK(r->horizon >= 1 && r->horizon <= 0x7fffffffll, OGBX_EINVAL, who + "horizon must lie in [1, 2^31)");
-  OGBX_CHECK(r->num_envs * r->horizon < kOnlineMaxRows, OGBX_EINVAL, who + "num_envs * horizon must be below 2^46");
-  OGBX_CHECK(r->steps >= 0, OGBX_EINVAL, who + "steps must be >= 0");
-  return OGBX_OK;
 }
 
 template <int N>
@@ -315,18 +251,7 @@ ogbx_status ogbx_online_gc_sample(const ogbx_online_ring* ring, const ogbx_gc_co
   const int64_t blocks = (total + tile - 1) / tile;
   OGBX_CHECK(blocks <= 0x7fffffffll, OGBX_EINVAL, who + "too many samples for one launch");
 
-  OnlineView v{};
-  v.ep_seq = ring->ep_seq;
-  v.cur_seq = ring->cur_seq;
-  v.ep_end = ring->ep_end;
-  v.n = ring->num_envs;
-  v.horizon = ring->horizon;
-  v.live = std::min(ring->steps, ring->horizon);
-  v.first = ring->steps - v.live;
-  v.last = ring->steps - 1;
-  v.slot0 = v.first % v.horizon;
-  v.npick = v.live * v.n;
-  v.inv_live = 1.0 / (double)v.live;
+  const OnlineView v = online_view(*ring);
   const ogbx_gc_draws dr = draws ? *draws : ogbx_gc_draws{};
   const GcParams pr = gc_params(seed, *cfg, nullptr);
   const auto kern = any_draw(dr) ? online_gc_sample_kernel<true> : online_gc_sample_kernel<false>;

@@ -340,6 +340,13 @@ def _bind():
         L.ogbx_online_gc_sample.restype = ctypes.c_int32
         L.ogbx_online_gc_sample.argtypes = [P(OnlineRing), P(GcConfig), P(OnlineBatch), P(GcDraws), P(GcDrawRecord),
                                             ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        # include/ogbx_online_hgc.h (likewise)
+        L.ogbx_online_hgc_api_version.restype = ctypes.c_int32
+        L.ogbx_online_hgc_api_version.argtypes = []
+        L.ogbx_online_hgc_sample.restype = ctypes.c_int32
+        L.ogbx_online_hgc_sample.argtypes = [P(OnlineRing), P(GcConfig), P(HgcConfig), ctypes.c_void_p, ctypes.c_int32,
+                                             ctypes.c_int64, P(HgcDraws), P(HgcOutputs), P(HgcDrawRecord),
+                                             ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
         L._gc_bound = True
     return L
 
@@ -2381,3 +2388,186 @@ class GCReplayBuffer(Dataset):
         term[:, :-1] = (seq[:, 1:] != seq[:, :-1]).to(torch.float32)  # the next live row belongs to another episode
         data['terminals'] = term.reshape(-1)
         return Dataset(data, device=self.device)
+
+
+class HGCReplayBuffer(GCReplayBuffer):
+    """Hierarchical hindsight sampling over the episode ring of
+    ``GCReplayBuffer``: the same constructor, inserts, ``clear``, ``snapshot``
+    and state, and a ``sample`` that returns what the reference's
+    ``HGCDataset.sample`` (datasets.py:496-643) returns over the snapshot
+    (include/ogbx_online_hgc.h).
+
+    The config also reads ``subgoal_steps`` and the optional
+    ``high_subgoal_steps``, ``value_subgoal_steps``, ``actor_subgoal_steps``,
+    ``low_subgoal_steps`` and ``low_discount``, resolved as
+    ``HGCDataset.__init__`` resolves them.
+
+    ``sample`` is ONE launch of ``online_hgc_sample_kernel`` and returns, bit
+    for bit, ``HGCDataset(Dataset(snapshot), config).sample`` under the same
+    draws -- with the Philox draws at one ``(seed, call)`` too -- for the
+    buffer's own keys followed by ``high_value_reps`` ..
+    ``low_actor_next_observations`` in the reference's order, with its aliases
+    (``high_value_reps is observations``, ``value_goals is high_value_goals``,
+    ``high_actor_targets is high_actor_actions``).  The goal-type keys come
+    from ``oracle_reps`` when the buffer has that column, else from
+    ``observations``.  Every index it takes or reports is a flat index of the
+    snapshot.  Nothing is read back.
+    """
+
+    _HGC_KEYS = ('high_value_reps', 'high_value_goals', 'high_value_actions', 'high_value_next_observations',
+                 'high_value_offsets', 'high_value_subgoal_steps', 'high_value_masks', 'high_value_rewards',
+                 'low_value_next_observations', 'low_value_subgoal_steps', 'low_value_masks', 'low_value_rewards',
+                 'low_value_goals', 'high_actor_goals', 'high_actor_actions', 'high_actor_next_observations',
+                 'high_actor_targets', 'low_actor_goals', 'low_actor_goal_observations',
+                 'low_actor_next_observations')
+    RESERVED = GCReplayBuffer.RESERVED + _HGC_KEYS
+    MAX_SAMPLE_COLS = 32  # kGcMaxCols
+
+    def __init__(self, data, num_envs, horizon, config, device=None, seed=None):
+        super().__init__(data, num_envs, horizon, config, device=device, seed=seed)
+        c = config
+        high = c.get('high_subgoal_steps', c['subgoal_steps'])
+        self.value_subgoal_steps = int(high if c.get('value_subgoal_steps') is None else c['value_subgoal_steps'])
+        self.actor_subgoal_steps = int(high if c.get('actor_subgoal_steps') is None else c['actor_subgoal_steps'])
+        self.low_subgoal_steps = int(c.get('low_subgoal_steps', c['subgoal_steps']))
+        if min(self.value_subgoal_steps, self.actor_subgoal_steps, self.low_subgoal_steps) < 1:
+            raise ValueError('subgoal steps must be >= 1')
+        self._has_low = c.get('low_discount') is not None
+        self._draw_keys = _DRAW_ORDER + (_HDRAW_LOW if self._has_low else ())
+        self._hv_tab = _subgoal_tables(c['discount'], self.value_subgoal_steps, c['gc_negative'], self.device)
+        self._lv_tab = _subgoal_tables(c['discount'], self.low_subgoal_steps, c['gc_negative'], self.device)
+        self._hcfg = HgcConfig(
+            self.value_subgoal_steps, self.low_subgoal_steps, self.actor_subgoal_steps, int(self._has_low), 0,
+            float(c['low_discount']) if self._has_low else 0.0,
+            self._hv_tab[0].data_ptr(), self._hv_tab[1].data_ptr(),
+            self._lv_tab[0].data_ptr(), self._lv_tab[1].data_ptr(),
+        )
+
+    # ----------------------------------------------------------------- sampling
+    def _batch(self, B, record):
+        """Output tensors in the reference's key order (HGCDataset._hcolumns),
+        the column descriptors and the scalar outputs."""
+        torch = _torch()
+        out, cols = {}, []
+
+        def col(src_key, select):
+            src = self[src_key]
+            if len(src) != self.rows or not src.is_contiguous() or src.device != self.device:
+                raise ValueError(f'buffer column {src_key!r} was replaced by one of another length, layout or device')
+            dst = torch.empty((B,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
+            row_bytes = (src[0].numel() if src.dim() > 1 else 1) * src.element_size()
+            cols.append(GcColumn(src.data_ptr(), dst.data_ptr(), row_bytes, select, 0))
+            return dst
+
+        def scalar(dtype):
+            return torch.empty(B, dtype=dtype, device=self.device)
+
+        for k in self.keys():
+            out[k] = col(k, 0)
+        goal_src = 'oracle_reps' if 'oracle_reps' in self else 'observations'  # datasets.py:348-357
+        i64, f64 = torch.int64, torch.float64
+        out['high_value_reps'] = out['observations']
+        out['high_value_goals'] = col(goal_src, 2)
+        out['high_value_actions'] = col(goal_src, 4)
+        out['high_value_next_observations'] = col('observations', 4)
+        for k, dt in (('high_value_offsets', i64), ('high_value_subgoal_steps', i64), ('high_value_masks', f64),
+                      ('high_value_rewards', f64)):
+            out[k] = scalar(dt)
+        out['low_value_next_observations'] = col('observations', 5)
+        for k, dt in (('low_value_subgoal_steps', i64), ('low_value_masks', f64), ('low_value_rewards', f64)):
+            out[k] = scalar(dt)
+        if self._has_low:
+            out['low_value_goals'] = col(goal_src, 6)
+        out['value_goals'] = out['high_value_goals']
+        out['masks'] = scalar(f64)
+        out['rewards'] = scalar(f64)
+        out['high_actor_goals'] = col(goal_src, 3)
+        out['high_actor_actions'] = col(goal_src, 7)
+        out['high_actor_next_observations'] = col('observations', 7)
+        out['high_actor_targets'] = out['high_actor_actions']
+        out['low_actor_goals'] = col(goal_src, 8)
+        out['low_actor_goal_observations'] = col('observations', 8)
+        out['low_actor_next_observations'] = col('observations', 9)
+        if len(cols) > self.MAX_SAMPLE_COLS:
+            raise ValueError(f'at most {self.MAX_SAMPLE_COLS} columns per sample, got {len(cols)}')
+        idx_t = {k: torch.empty(B, dtype=i64, device=self.device) for k in (_HGC_SCALARS[:4] if record else ())}
+        outs = HgcOutputs(*[_lib.ptr(idx_t.get(k)) for k in _HGC_SCALARS[:4]],
+                          *[out[k].data_ptr() for k in _HGC_SCALARS[4:]])
+        arr = (GcColumn * len(cols))(*cols)
+        return out, (arr, len(cols), outs), {'_' + k: t for k, t in idx_t.items()}
+
+    def sample(self, batch_size, idxs=None, draws=None, record_draws=False, out=None):
+        """HGCDataset.sample (datasets.py:496-643) over the snapshot, one
+        launch.  Raises ValueError while no step was inserted.
+
+        idxs: explicit flat rows of the snapshot, clamped into ``[0, L * N)``.
+        draws: injected reference draws (``_DRAW_ORDER``, with ``low_discount``
+        also the ``l_*`` draws), picks as flat rows.
+        record_draws: also return the draws used (``out['_draws']``; the
+        ``l_*`` draws only with ``low_discount``) and the flat ``_idxs`` /
+        ``_high_value_goal_idxs`` / ``_high_actor_goal_idxs`` /
+        ``_low_value_goal_idxs``.
+        out: a batch returned by an earlier plain call with the same
+        batch_size: refilled in place, stream ordered, and returned (a batch
+        of another size raises ValueError).
+        """
+        torch = _torch()
+        B = int(batch_size)
+        if self._steps == 0:
+            raise ValueError('cannot sample from an empty HGCReplayBuffer')
+        plain = idxs is None and not draws and not record_draws
+        if self._out_gen != self._gen:  # a column was replaced
+            self._out_cache.clear()
+            self._out_gen = self._gen
+        hit = self._out_cache.get(id(out)) if (out is not None and plain) else None
+        if hit is not None and hit[0] is out and hit[1] == B:
+            call = self._calls
+            self._calls = call + 1
+            arr, ncols, outs = hit[2]
+            st = self._L.ogbx_online_hgc_sample(self._ring, self._cfg, self._hcfg, arr, ncols, B, None, outs, None,
+                                                 self._seed, call, self._raw_stream(self._dev_idx))
+            if st:
+                _lib.check(st, 'online_hgc_sample')
+            return out
+        if out is not None and len(out['masks']) != B:
+            raise ValueError(f"out= holds a batch of {len(out['masks'])} samples, not {B}")
+        out, held, idx_t = self._batch(B, record_draws)
+        dr = rec = rec_t = None
+        staged = []
+        if idxs is not None or draws:
+            dr = HgcDraws()
+            if idxs is not None:
+                t = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
+                if t.numel() != B:
+                    raise ValueError(f'idxs must have {B} entries, got {t.numel()}')
+                staged.append(t)
+                dr.gc.idxs = t.data_ptr()
+            for k, v in (draws or {}).items():
+                if k == 'idxs':
+                    continue
+                if k not in self._draw_keys:
+                    raise ValueError(f'unknown draw {k!r}')
+                t = _to_device(v, self.device).to(torch.int64 if k in _HDRAW_INT else torch.float64).reshape(-1)
+                if t.numel() != B:
+                    raise ValueError(f'draw {k!r} must have {B} entries, got {t.numel()}')
+                staged.append(t)
+                setattr(dr if k in _HDRAW_LOW else dr.gc, k, t.data_ptr())
+        if record_draws:
+            rec_t = {k: torch.empty(B, dtype=torch.int64 if k in _HDRAW_INT else torch.float64, device=self.device)
+                     for k in self._draw_keys}
+            rec = HgcDrawRecord(GcDrawRecord(*[rec_t[k].data_ptr() for k in _DRAW_ORDER]),
+                                *[_lib.ptr(rec_t.get(k)) for k in _HDRAW_LOW])
+        seed, call = self._next_seed()
+        arr, ncols, outs = held
+        st = self._L.ogbx_online_hgc_sample(self._ring, self._cfg, self._hcfg, arr, ncols, B, dr, outs, rec, seed,
+                                             call, self._raw_stream(self._dev_idx))
+        _lib.check(st, 'online_hgc_sample')
+        del staged  # alive until the launch was issued
+        if plain:
+            if len(self._out_cache) >= 2:
+                self._out_cache.clear()
+            self._out_cache[id(out)] = (out, B, held)
+        if record_draws:
+            out['_draws'] = rec_t
+            out.update(idx_t)
+        return out
