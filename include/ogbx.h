@@ -702,7 +702,10 @@ ogbx_status ogbx_compact_terminals(const float* terminals_in, int64_t n, float* 
 
 /* dst[k] = src[idx[k]] for rows of row_bytes bytes (k < n).  With idx from
  * ogbx_nonzero_f32 this is the regular-dataset mask compaction
- * (utils.py:77-94: observations[ob_mask], observations[next_ob_mask], ...). */
+ * (utils.py:77-94: observations[ob_mask], observations[next_ob_mask], ...).
+ * src, idx and dst need no alignment beyond their element types (rows are
+ * copied in the widest unit that row_bytes and both addresses allow).  n = 0
+ * is a no-op, and idx and dst may then be NULL. */
 ogbx_status ogbx_gather_rows(const void* src, int64_t row_bytes, const int64_t* idx, int64_t n, void* dst,
                              void* stream);
 
@@ -724,8 +727,13 @@ ogbx_status ogbx_relabel_maze(const void* qpos, int32_t qpos_is_f64, int64_t num
  * 1} and remaining[i] -= 1.  All pointers are device memory: success /
  * terminated / truncated u8[n] (a step's outputs), task_id i32[n] (1-based),
  * remaining i32[n] (in/out), counters int64[num_tasks, 2] = {success_sum,
- * episode_count} (accumulated, never cleared here; num_tasks <= 64).  The
- * counter block is what ranks all-gather at the end of evaluation. */
+ * episode_count} (accumulated, never cleared here; 1 <= num_tasks <= 64, any
+ * other value is OGBX_EINVAL and nothing is written).  success counts as 1
+ * whenever its byte is non-zero.  A row whose task_id is outside
+ * 1..num_tasks adds to no counter, but its episode still ended: remaining[i]
+ * is decremented like any other.  n = 0 is a no-op, and the per-env pointers
+ * may then be NULL.  The counter block is what ranks all-gather at the end of
+ * evaluation. */
 ogbx_status ogbx_eval_accumulate(const uint8_t* success, const uint8_t* terminated,
                                  const uint8_t* truncated, const int32_t* task_id,
                                  int32_t* remaining, int64_t n, int32_t num_tasks, int64_t* counters,

@@ -25,8 +25,8 @@ __global__ void __launch_bounds__(256) eval_accumulate_kernel(
   __syncthreads();
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     if ((terminated[i] | truncated[i]) && remaining[i] > 0) {
-      const int t = task_id[i] - 1;
-      if (t >= 0 && t < num_tasks) {
+      const unsigned int t = (unsigned int)task_id[i] - 1u;  // ids <= 0 wrap past every valid slot
+      if (t < (unsigned int)num_tasks) {
         atomicAdd(&s_cnt[t][0], success[i] ? 1u : 0u);
         atomicAdd(&s_cnt[t][1], 1u);
       }
@@ -50,11 +50,12 @@ ogbx_status ogbx_eval_accumulate(const uint8_t* success, const uint8_t* terminat
                                  const uint8_t* truncated, const int32_t* task_id,
                                  int32_t* remaining, int64_t n, int32_t num_tasks, int64_t* counters,
                                  void* stream) {
-  OGBX_CHECK(success && terminated && truncated && task_id && remaining && counters, OGBX_EINVAL,
-             "ogbx_eval_accumulate: null argument");
   OGBX_CHECK(n >= 0 && num_tasks >= 1 && num_tasks <= kEvalMaxTasks, OGBX_EINVAL,
              "ogbx_eval_accumulate: bad n or num_tasks (1..64)");
-  if (n == 0) return OGBX_OK;
+  OGBX_CHECK(counters, OGBX_EINVAL, "ogbx_eval_accumulate: null argument");
+  if (n == 0) return OGBX_OK;  // no envs: the per-env buffers are zero-byte, NULL in practice
+  OGBX_CHECK(success && terminated && truncated && task_id && remaining, OGBX_EINVAL,
+             "ogbx_eval_accumulate: null argument");
   const int64_t blocks = std::min<int64_t>((n + 255) / 256, 1024);
   hipLaunchKernelGGL(eval_accumulate_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream,
                      success, terminated, truncated, task_id, remaining, n, num_tasks,

@@ -90,8 +90,9 @@ ogbx_status ogbx_compact_terminals(const float* terminals_in, int64_t n, float* 
 
 ogbx_status ogbx_gather_rows(const void* src, int64_t row_bytes, const int64_t* idx, int64_t n, void* dst,
                              void* stream) {
-  OGBX_CHECK(src && idx && dst && row_bytes > 0 && n >= 0, OGBX_EINVAL, "ogbx_gather_rows: bad argument");
-  if (n == 0) return OGBX_OK;
+  OGBX_CHECK(src && row_bytes > 0 && n >= 0, OGBX_EINVAL, "ogbx_gather_rows: bad argument");
+  if (n == 0) return OGBX_OK;  // an empty selection: idx and dst are zero-byte buffers, NULL in practice
+  OGBX_CHECK(idx && dst, OGBX_EINVAL, "ogbx_gather_rows: null idx or dst");
   const uintptr_t a = (uintptr_t)src | (uintptr_t)dst;
   hipStream_t s = (hipStream_t)stream;
   auto launch = [&](auto tag) {

@@ -15,10 +15,10 @@ recorded np.random draws.
 import numpy as np
 
 
-def load_dataset(raw, compact_dataset=False, add_info=False):
+def load_dataset(raw, compact_dataset=False, add_info=False, ob_dtype=np.float32, action_dtype=np.float32):
     """ogbench/utils.py:14-96 on an in-memory dict of the .npz arrays."""
-    d = {'observations': raw['observations'].astype(np.float32),
-         'actions': raw['actions'].astype(np.float32),
+    d = {'observations': raw['observations'].astype(ob_dtype),
+         'actions': raw['actions'].astype(action_dtype),
          'terminals': raw['terminals'].astype(np.float32)}
     info = [k for k in ('qpos', 'qvel', 'button_states') if add_info and k in raw]
     for k in info:
