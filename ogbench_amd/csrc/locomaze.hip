@@ -1,5 +1,6 @@
 // locomaze.hip -- batched pointmaze envs on gfx950: reset / step / physics kernels
-// and their C-ABI (include/ogbx.h).
+// and their C-ABI (include/ogbx.h; the fused collector of include/ogbx_collect.h
+// through collect_device.h).
 //
 // Layout in HBM (one handle = one batch of N envs on one device):
 //   qpos    f64[N,2]  (x, y interleaved: one 16-B load/store per lane)
@@ -847,6 +848,7 @@ __global__ void set_goal_kernel(const MazeParams* __restrict__ Pp, MazeState S, 
 }  // namespace ogbx
 
 #include "antmaze.h"
+#include "collect_device.h"
 
 namespace ogbx {
 
@@ -1481,6 +1483,63 @@ ogbx_status ogbx_maze_set_goal(ogbx_maze_t e, const int32_t* goal_ij, const uint
   hipLaunchKernelGGL(set_goal_kernel, dim3(grid_for(e->n, 256)), dim3(256), 0, (hipStream_t)stream, e->Pd, e->S,
                      e->n, goal_ij, mask, noise, k0, k1, (uint32_t)call_index, (uint32_t)(call_index >> 32));
   OGBX_LAUNCHED("set_goal_kernel");
+  return OGBX_OK;
+}
+
+// ------------------------------------------------- include/ogbx_collect.h
+
+int32_t ogbx_collect_abi_version(void) { return OGBX_COLLECT_ABI_VERSION; }
+
+ogbx_status ogbx_maze_collect(ogbx_maze_t e, const ogbx_collect_config* cfg, const ogbx_collect_tape* tape,
+                              int32_t t0, int32_t k_steps, uint64_t seed, const ogbx_collect_outputs* out,
+                              void* stream) {
+  OGBX_CHECK(e != nullptr && cfg != nullptr && out != nullptr, OGBX_EINVAL, "ogbx_maze_collect: null argument");
+  OGBX_CHECK(e->P.loco_type == 0, OGBX_EINVAL,
+             "ogbx_maze_collect: only the point agent has an oracle actor (not a point handle)");
+  OGBX_CHECK(e->P.terminate_at_goal == 0, OGBX_EINVAL,
+             "ogbx_maze_collect: collection runs whole episodes, create the handle with terminate_at_goal = 0");
+  OGBX_CHECK(out->observations && out->actions && out->terminals && out->qpos, OGBX_EINVAL,
+             "ogbx_maze_collect: null dataset column");
+  OGBX_CHECK(k_steps > 0 && t0 >= 0, OGBX_EINVAL, "ogbx_maze_collect: k_steps must be >= 1 and t0 >= 0");
+  const int64_t t1 = (int64_t)t0 + k_steps;
+  OGBX_CHECK(t1 <= e->P.max_steps, OGBX_EINVAL,
+             "ogbx_maze_collect: the chunk runs past the time limit (t0 + k_steps > max_episode_steps = " +
+                 std::to_string(e->P.max_steps) + ")");
+  OGBX_CHECK(t1 <= out->row_stride && out->row_offset >= 0, OGBX_EINVAL,
+             "ogbx_maze_collect: the chunk runs past row_stride, or row_offset < 0");
+  const int mode = cfg->mode;
+  OGBX_CHECK(mode >= OGBX_COLLECT_PATH && mode <= OGBX_COLLECT_EXPLORE, OGBX_EINVAL,
+             "ogbx_maze_collect: unknown mode");
+  OGBX_CHECK(cfg->explore_period > 0, OGBX_EINVAL, "ogbx_maze_collect: explore_period must be positive");
+  OGBX_CHECK(cfg->noise >= 0.0 && std::isfinite(cfg->noise), OGBX_EINVAL,
+             "ogbx_maze_collect: noise must be finite and >= 0");
+  OGBX_CHECK(mode != OGBX_COLLECT_NAVIGATE || (cfg->goal_cells != nullptr && cfg->n_goal_cells > 0), OGBX_EINVAL,
+             "ogbx_maze_collect: navigate needs goal cells");
+  CollectArgs A{};
+  if (tape != nullptr) {
+    const bool any = tape->normal || tape->goal_pick || tape->goal_noise || tape->dir;
+    OGBX_CHECK(!any || tape->steps >= t1, OGBX_EINVAL, "ogbx_maze_collect: the chunk runs past the tape");
+    A.tape = *tape;
+  }
+  OGBX_CHECK(e->was_reset, OGBX_ESTATE, "Cannot call env.collect() before calling env.reset()");
+  OGBX_HIP(hipSetDevice(e->device));
+  A.Pp = e->Pd;
+  A.bfs = e->bfs;
+  A.C = e->C;
+  A.S = e->S;
+  A.n = e->n;
+  A.cfg = *cfg;
+  A.out = *out;
+  A.t0 = t0;
+  A.k_steps = k_steps;
+  seed_key(seed, kTagMazeCollect, &A.k0, &A.k1);
+  // the teleport out-portal draw of a fused step is that of the single step it stands for
+  seed_key(e->seed, kTagMazeReset, &A.sk0, &A.sk1);
+  auto* kern = mode == OGBX_COLLECT_NAVIGATE  ? maze_collect_kernel<OGBX_COLLECT_NAVIGATE>
+               : mode == OGBX_COLLECT_EXPLORE ? maze_collect_kernel<OGBX_COLLECT_EXPLORE>
+                                              : maze_collect_kernel<OGBX_COLLECT_PATH>;
+  hipLaunchKernelGGL(kern, dim3(grid_for(e->n, kStepBlock)), dim3(kStepBlock), 0, (hipStream_t)stream, A);
+  OGBX_LAUNCHED("maze_collect_kernel");
   return OGBX_OK;
 }
 

@@ -431,6 +431,7 @@ class MazeEnv:
         m = None
         if mask is not None:
             m = torch.as_tensor(mask).to(self.device, torch.uint8).contiguous()
+        self._collect_t = 0 if mask is None else None  # collect(): episode step of envs in lock step
         if self._loco_env_type == 'ant':
             bd = options.get('body_draws')
             if bd is not None:
@@ -683,6 +684,107 @@ class MazeEnv:
             'rollout_until_done',
         )
         return out
+
+    def collect(self, k_steps, out, mode, noise=0.2, goal_cells=None, tape=None, seed=None, diagnostics=False):
+        """k_steps fused data-collection steps of every env in ONE launch
+        (include/ogbx_collect.h): per step the point-maze expert of
+        data_gen_scripts/generate_locomaze.py:147-175 -- subgoal direction
+        ('path', 'stitch', 'navigate') or a random direction held for 10 steps
+        ('explore'), Gaussian action noise, clip -- then ``step`` with that
+        float64 action, and for 'navigate' a new goal for the envs that reached
+        theirs.  The same arithmetic as ``expert_action`` -> ``step`` ->
+        ``set_goal``, bit for bit; needs terminate_at_goal=False.
+
+        out: dict of the preallocated dataset tensors, written in place in
+        trajectory-major rows: ``observations``, ``actions``, ``qpos`` float32
+        [rows, 2] and ``terminals`` bool / uint8 [rows]; ``row_offset`` (row of
+        env 0 at episode step 0, default 0) and ``row_stride`` (rows per episode,
+        default max_episode_steps).  Env e writes row row_offset + e *
+        row_stride + t at episode step t.
+        The episode step is tracked from the last unmasked ``reset`` and counts
+        the steps of ``collect`` only (envs run in lock step); out['t0'] overrides
+        it.  A chunk past max_episode_steps raises ValueError.
+        goal_cells: int [n, 2] (i, j) cells 'navigate' resamples from.
+        tape: dict of injected draws indexed by episode step (all optional):
+        ``normal`` f64 [T, N, 2] finished N(0, noise) samples, ``goal_pick`` i32
+        [T, N], ``goal_noise`` f64 [T, N, 2] uniform(-1, 1), ``dir`` f64
+        [ceil(T / 10), N, 2] raw standard normals.  Otherwise Philox keyed by
+        ``seed`` (default: the env's seed), the global env index and the step.
+        Returns a dict: empty, or with ``diagnostics`` the chunk's ``qpos64`` and
+        ``goal64`` f64 [K, N, 2] (state and goal before each step) and
+        ``success`` bool [K, N]."""
+        from . import _collect
+
+        torch = _torch()
+        if mode not in _collect.MODES:
+            raise ValueError(f'mode must be one of {tuple(_collect.MODES)}, got {mode!r}')
+        if not self._is_point:
+            raise ValueError('collect: only the point agent has an oracle actor (ant/humanoid experts are SAC nets)')
+        if self._terminate_at_goal:
+            raise ValueError('collect: collection runs whole episodes, make the env with terminate_at_goal=False')
+        if not isinstance(k_steps, (int, np.integer)) or isinstance(k_steps, bool) or k_steps <= 0:
+            raise ValueError(f'k_steps must be a positive int, got {k_steps!r}')
+        n, K = self.num_envs, int(k_steps)
+        t0 = out.get('t0', getattr(self, '_collect_t', None))
+        if t0 is None:
+            raise ValueError('collect needs envs in lock step: call reset() (without a mask) first, or give out["t0"]')
+        t0 = int(t0)
+        if t0 + K > self.max_episode_steps:
+            raise ValueError(f'collect: steps {t0}..{t0 + K - 1} run past the time limit '
+                             f'(max_episode_steps = {self.max_episode_steps})')
+        stride = int(out.get('row_stride', self.max_episode_steps))
+        offset = int(out.get('row_offset', 0))
+        if offset < 0 or stride < t0 + K:
+            raise ValueError(f'collect: row_offset {offset} / row_stride {stride} do not hold steps {t0}..{t0 + K - 1}')
+        rows = offset + n * stride
+        for k in _collect.COLUMNS:
+            t = out.get(k)
+            wide = k != 'terminals'
+            if (not isinstance(t, torch.Tensor) or t.device != self.device or not t.is_contiguous()
+                    or t.dtype not in ((torch.float32,) if wide else (torch.bool, torch.uint8))
+                    or t.dim() != (2 if wide else 1) or t.shape[0] < rows or (wide and t.shape[1] != 2)):
+                raise ValueError(f'collect: out[{k!r}] must be a contiguous {"float32 [rows, 2]" if wide else "bool [rows]"}'
+                                 f' tensor on {self.device} with rows >= {rows}')
+        steps = _collect.check_tape(tape, n)
+        if steps and steps < t0 + K:
+            raise ValueError(f'collect: the tape covers {steps} steps, the chunk ends at step {t0 + K}')
+        cells = None
+        if mode == 'navigate':
+            if goal_cells is None:
+                raise ValueError("collect: 'navigate' needs goal_cells")
+            cells = torch.as_tensor(goal_cells).to(self.device, torch.int32).contiguous()
+            if cells.dim() != 2 or cells.shape[1] != 2 or cells.shape[0] < 1:
+                raise ValueError(f'goal_cells must be int [n >= 1, 2], got {tuple(cells.shape)}')
+        L = _collect.bind()
+        cfg = _collect.CollectConfig(mode=_collect.MODES[mode], explore_period=_collect.EXPLORE_PERIOD,
+                                     noise=float(noise), goal_cells=None if cells is None else cells.data_ptr(),
+                                     n_goal_cells=0 if cells is None else cells.shape[0])
+        tp, keep = None, [cells]
+        if steps:
+            dt = dict(normal=torch.float64, goal_pick=torch.int32, goal_noise=torch.float64, dir=torch.float64)
+            ptrs = {}
+            for k in _collect.TAPE_KEYS:
+                if tape.get(k) is not None:
+                    v = torch.as_tensor(tape[k]).to(self.device, dt[k]).contiguous()
+                    keep.append(v)
+                    ptrs[k] = v.data_ptr()
+            tp = _collect.CollectTape(steps=steps, **ptrs)
+        diag = {}
+        if diagnostics:
+            diag = dict(qpos64=torch.empty(K, n, 2, dtype=torch.float64, device=self.device),
+                        goal64=torch.empty(K, n, 2, dtype=torch.float64, device=self.device),
+                        success=torch.empty(K, n, dtype=torch.bool, device=self.device))
+        o = _collect.CollectOutputs(row_stride=stride, row_offset=offset,
+                                    **{k: out[k].data_ptr() for k in _collect.COLUMNS},
+                                    **{k: v.data_ptr() for k, v in diag.items()})
+        sd = seed if seed is not None else (self._seed if self._seed is not None else 0)
+        with torch.cuda.device(self.device):
+            _lib.check(L.ogbx_maze_collect(self._h, cfg, tp, t0, K, int(sd) & ((1 << 64) - 1), o, self._stream()),
+                       'collect')
+        self._collect_keep = keep  # inputs of the launch in flight stay referenced until the next one
+        if 't0' not in out:
+            self._collect_t = t0 + K
+        return diag
 
     def physics(self, qpos, action):
         """Free-standing PointEnv physics (point.py:68-73) for [n,2] qpos/actions."""
