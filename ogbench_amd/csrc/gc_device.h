@@ -2,7 +2,10 @@
 // share: the per-sample draw chain (index loads, goal relabel), the tile
 // helpers (Philox words, XCD-major numbering, row copies) and the host-side
 // argument checks and launch parameters of the ogbx_gc_* / ogbx_hgc_* /
-// ogbx_trl_* entry points.  Internal to libogbx.
+// ogbx_trl_* entry points.  The samplers of replay.hip, online.hip and
+// online_hgc.hip take the tile helpers, the goal draws and their record
+// (goal_side_draws, store_draw_record) and the gather-column check
+// (check_gather_columns) from here too.  Internal to libogbx.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -134,6 +137,49 @@ __device__ inline int64_t geometric_from(double u, double log_q) {
   // legacy RandomState.geometric inversion: ceil(log(1-u) / log(1-p))
   double g = ceil(log(1.0 - u) / log_q);
   return g < 1.0 ? 1 : (int64_t)g;
+}
+
+// The eight draws of the value and actor goals besides the picks, in the slot
+// layout every sampler shares (words w1.zw .. w4.xy of sample s); an injected
+// draw replaces its Philox value in the kInj instances.  The picks stay with
+// the kernels: they load with the index loads, and the ring clamps them.
+// A kernel calls this only where its gfx950 code is the written-out block's,
+// instruction for instruction (profiles/buffer_refactor_isa.txt):
+// hgc_sample_kernel (gcsample.hip) keeps the block written out -- through the
+// helper both of its instances came out 5 and 7 instructions longer with
+// another SGPR assignment.
+template <bool kInj>
+__device__ __forceinline__ void goal_side_draws(const ogbx_gc_draws& dr, const ogbx_gc_config& cfg, int64_t s,
+                                                const u32x4& w1, const u32x4& w2, const u32x4& w3, const u32x4& w4,
+                                                double v_log_q, double a_log_q, GoalDraws& v, GoalDraws& a) {
+  const double uvg = u01_from(w1.z, w1.w), uag = u01_from(w2.x, w2.y);
+  v.geom = (kInj && dr.v_geom) ? dr.v_geom[s] : (cfg.value_geom_sample ? geometric_from(uvg, v_log_q) : 0);
+  a.geom = (kInj && dr.a_geom) ? dr.a_geom[s] : (cfg.actor_geom_sample ? geometric_from(uag, a_log_q) : 0);
+  v.dist = (kInj && dr.v_dist) ? dr.v_dist[s] : uvg;
+  a.dist = (kInj && dr.a_dist) ? dr.a_dist[s] : uag;
+  v.u_traj = (kInj && dr.v_u_traj) ? dr.v_u_traj[s] : u01_from(w2.z, w2.w);
+  v.u_cur = (kInj && dr.v_u_cur) ? dr.v_u_cur[s] : u01_from(w3.x, w3.y);
+  a.u_traj = (kInj && dr.a_u_traj) ? dr.a_u_traj[s] : u01_from(w3.z, w3.w);
+  a.u_cur = (kInj && dr.a_u_cur) ? dr.a_u_cur[s] : u01_from(w4.x, w4.y);
+}
+
+// The draws sample s used, to the record of a recording call (rec.pick NULL:
+// none).  pick is -1 where the call gave the row itself.
+__device__ __forceinline__ void store_draw_record(const ogbx_gc_draw_record& rec, int64_t s, int64_t pick,
+                                                  const GoalDraws& v, const GoalDraws& a) {
+  if (rec.pick) {
+    rec.pick[s] = pick;
+    rec.v_pick[s] = v.pick;
+    rec.v_geom[s] = v.geom;
+    rec.v_dist[s] = v.dist;
+    rec.v_u_traj[s] = v.u_traj;
+    rec.v_u_cur[s] = v.u_cur;
+    rec.a_pick[s] = a.pick;
+    rec.a_geom[s] = a.geom;
+    rec.a_dist[s] = a.dist;
+    rec.a_u_traj[s] = a.u_traj;
+    rec.a_u_cur[s] = a.u_cur;
+  }
 }
 
 // Threads [t0, blockDim.x) copy (t0 = 64: the first wave is busy elsewhere).
@@ -274,14 +320,14 @@ __device__ inline u32x4 tile_word(const uint4 (*wb)[kGcMaxTile], int q, int b) {
 // ---------------------------------------------------------------- host side
 // Every column 4-byte granular and aligned with rows of <= 128 words (the
 // per-wave job copy of copy_tile).
-static bool flat4_columns(const GcColumns& cc, int num_cols) {
+static bool flat4_columns(const ogbx_gc_column* cols, int num_cols) {
+  bool flat4 = true;
   for (int i = 0; i < num_cols; ++i) {
-    const ogbx_gc_column& c = cc.c[i];
-    if (c.row_bytes % 4 != 0 || c.row_bytes > 512 ||
-        ((uintptr_t)c.src | (uintptr_t)c.dst | (uintptr_t)c.src_stride) % 4 != 0)
-      return false;
+    const ogbx_gc_column& c = cols[i];
+    flat4 = flat4 && c.row_bytes % 4 == 0 && c.row_bytes <= 512 &&
+            ((uintptr_t)c.src | (uintptr_t)c.dst | (uintptr_t)c.src_stride) % 4 == 0;
   }
-  return true;
+  return flat4;
 }
 
 // True when any draw is injected (parity replays); the Philox-only kernels
@@ -319,21 +365,44 @@ static ogbx_status check_buffer(const ogbx_gc_buffer* buf) {
   return OGBX_OK;
 }
 
+// The descriptors of a gather-column table of num_cols entries (the count is
+// the entry point's to check), column by column: bit k of `selects` allows
+// select code k.  Copies the table to *cc (the kernel argument; NULL: not
+// here) and tells whether copy_tile may take its per-wave job copy (*flat4).
+// The entry points word their rejects in two ways, each pinned by its tests:
+//   kSplitNull (replay and ring): "null column pointer" on its own and first,
+//     then "bad column descriptor", then the stride;
+//   otherwise (ogbx_gc_* / ogbx_hgc_* / ogbx_trl_*): the stride first, then a
+//     null pointer folded into "bad column descriptor".
+template <bool kSplitNull, class Cols>
+static ogbx_status check_gather_columns(const ogbx_gc_column* cols, int32_t num_cols, uint32_t selects,
+                                        const char* who, Cols* cc, bool* flat4) {
+  for (int i = 0; i < num_cols; ++i) {
+    const ogbx_gc_column& c = cols[i];
+    const bool ptrs = c.src && c.dst;
+    const bool desc = c.row_bytes > 0 && c.select >= 0 && c.select < 32 && ((selects >> c.select) & 1u);
+    if (kSplitNull) {
+      OGBX_CHECK(ptrs, OGBX_EINVAL, named(who, "null column pointer"));
+      OGBX_CHECK(desc, OGBX_EINVAL, named(who, "bad column descriptor"));
+    }
+    OGBX_CHECK(c.src_stride == 0 || c.src_stride >= c.row_bytes, OGBX_EINVAL, named(who, "src_stride below row_bytes"));
+    OGBX_CHECK(ptrs && desc, OGBX_EINVAL, named(who, "bad column descriptor"));
+    if (cc) cc->c[i] = c;
+  }
+  *flat4 = flat4_columns(cols, num_cols);
+  return OGBX_OK;
+}
+
+// Bits 0 .. max_select: the select codes of the dataset samplers.
+constexpr uint32_t selects_up_to(int max_select) { return (2u << max_select) - 1u; }
+
 // The batch shape and the column descriptors (select in [0, max_select]),
 // copied into the kernel-argument table *cc.
 static ogbx_status check_columns(const ogbx_gc_column* cols, int32_t num_cols, int64_t batch, int64_t num_batches,
-                                 int max_select, const char* who, GcColumns* cc) {
+                                 int max_select, const char* who, GcColumns* cc, bool* flat4) {
   OGBX_CHECK(num_cols >= 0 && num_cols <= kGcMaxCols, OGBX_EINVAL, named(who, "at most 32 columns"));
   OGBX_CHECK(batch > 0 && num_batches > 0, OGBX_EINVAL, "batch and num_batches must be > 0");
-  for (int i = 0; i < num_cols; ++i) {
-    const ogbx_gc_column& c = cols[i];
-    OGBX_CHECK(c.src_stride == 0 || c.src_stride >= c.row_bytes, OGBX_EINVAL,
-               named(who, "src_stride below row_bytes"));
-    OGBX_CHECK(c.src && c.dst && c.row_bytes > 0 && c.select >= 0 && c.select <= max_select, OGBX_EINVAL,
-               named(who, "bad column descriptor"));
-    cc->c[i] = c;
-  }
-  return OGBX_OK;
+  return check_gather_columns<false>(cols, num_cols, selects_up_to(max_select), who, cc, flat4);
 }
 
 // ------------------------------------------------- derived launch parameters

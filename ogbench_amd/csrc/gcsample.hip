@@ -75,15 +75,7 @@ __global__ void __launch_bounds__(256) gc_sample_kernel(
     const int64_t v_rand = cfg.value_cur_is_one ? 0 : rand_goal_of(buf, v.pick);
     const int64_t a_rand = cfg.actor_cur_is_one ? 0 : rand_goal_of(buf, a.pick);
     const int64_t next = idx + 1 < buf.num_rows ? idx + 1 : buf.num_rows - 1;
-    const double uvg = u01_from(w1.z, w1.w), uag = u01_from(w2.x, w2.y);
-    v.geom = (kInj && dr.v_geom) ? dr.v_geom[s] : (cfg.value_geom_sample ? geometric_from(uvg, v_log_q) : 0);
-    a.geom = (kInj && dr.a_geom) ? dr.a_geom[s] : (cfg.actor_geom_sample ? geometric_from(uag, a_log_q) : 0);
-    v.dist = (kInj && dr.v_dist) ? dr.v_dist[s] : uvg;
-    a.dist = (kInj && dr.a_dist) ? dr.a_dist[s] : uag;
-    v.u_traj = (kInj && dr.v_u_traj) ? dr.v_u_traj[s] : u01_from(w2.z, w2.w);
-    v.u_cur = (kInj && dr.v_u_cur) ? dr.v_u_cur[s] : u01_from(w3.x, w3.y);
-    a.u_traj = (kInj && dr.a_u_traj) ? dr.a_u_traj[s] : u01_from(w3.z, w3.w);
-    a.u_cur = (kInj && dr.a_u_cur) ? dr.a_u_cur[s] : u01_from(w4.x, w4.y);
+    goal_side_draws<kInj>(dr, cfg, s, w1, w2, w3, w4, v_log_q, a_log_q, v, a);
     const int64_t vg = sample_goal(idx, final_idx, v, v_rand, cfg.value_p_curgoal,
                                    cfg.value_traj_thresh, cfg.value_geom_sample, cfg.value_cur_is_one);
     const int64_t ag = sample_goal(idx, final_idx, a, a_rand, cfg.actor_p_curgoal,
@@ -99,19 +91,7 @@ __global__ void __launch_bounds__(256) gc_sample_kernel(
     const double succ = idx == vg ? 1.0 : 0.0;
     masks[s] = 1.0 - succ;
     rewards[s] = succ - (cfg.gc_negative ? 1.0 : 0.0);
-    if (rec.pick) {
-      rec.pick[s] = pick;
-      rec.v_pick[s] = v.pick;
-      rec.v_geom[s] = v.geom;
-      rec.v_dist[s] = v.dist;
-      rec.v_u_traj[s] = v.u_traj;
-      rec.v_u_cur[s] = v.u_cur;
-      rec.a_pick[s] = a.pick;
-      rec.a_geom[s] = a.geom;
-      rec.a_dist[s] = a.dist;
-      rec.a_u_traj[s] = a.u_traj;
-      rec.a_u_cur[s] = a.u_cur;
-    }
+    store_draw_record(rec, s, pick, v, a);
     }  // own
   }
   __syncthreads();
@@ -138,15 +118,7 @@ __device__ inline GcPick gc_chain(const ogbx_gc_buffer& buf, const ogbx_gc_confi
   index_loads(buf, false, pick, &idx, &final_idx);
   const int64_t v_rand = cfg.value_cur_is_one ? 0 : rand_goal_of(buf, v.pick);
   const int64_t a_rand = cfg.actor_cur_is_one ? 0 : rand_goal_of(buf, a.pick);
-  const double uvg = u01_from(w1.z, w1.w), uag = u01_from(w2.x, w2.y);
-  v.geom = cfg.value_geom_sample ? geometric_from(uvg, v_log_q) : 0;
-  a.geom = cfg.actor_geom_sample ? geometric_from(uag, a_log_q) : 0;
-  v.dist = uvg;
-  a.dist = uag;
-  v.u_traj = u01_from(w2.z, w2.w);
-  v.u_cur = u01_from(w3.x, w3.y);
-  a.u_traj = u01_from(w3.z, w3.w);
-  a.u_cur = u01_from(w4.x, w4.y);
+  goal_side_draws<false>(ogbx_gc_draws{}, cfg, 0, w1, w2, w3, w4, v_log_q, a_log_q, v, a);
   GcPick p;
   p.idx = idx;
   p.next = idx + 1 < buf.num_rows ? idx + 1 : buf.num_rows - 1;
@@ -320,6 +292,7 @@ __global__ void __launch_bounds__(256) hgc_sample_kernel(
     const int64_t a_rand = cfg.actor_cur_is_one ? 0 : rand_goal_of(buf, a.pick);
     if (hc.has_low_value_goals && !cfg.value_cur_is_one) l_rand = rand_goal_of(buf, l.pick);
     const int64_t next = idx + 1 < buf.num_rows ? idx + 1 : buf.num_rows - 1;
+    // written out, not goal_side_draws: the helper moves this kernel's code (gc_device.h)
     const double uvg = u01_from(w1.z, w1.w), uag = u01_from(w2.x, w2.y);
     v.geom = (kInj && g.v_geom) ? g.v_geom[s] : (cfg.value_geom_sample ? geometric_from(uvg, v_log_q) : 0);
     a.geom = (kInj && g.a_geom) ? g.a_geom[s] : (cfg.actor_geom_sample ? geometric_from(uag, a_log_q) : 0);
@@ -387,19 +360,7 @@ __global__ void __launch_bounds__(256) hgc_sample_kernel(
     const double succ = idx == hvg ? 1.0 : 0.0;
     o.masks[s] = 1.0 - succ;
     o.rewards[s] = succ - neg;
-    if (rec.gc.pick) {
-      rec.gc.pick[s] = pick;
-      rec.gc.v_pick[s] = v.pick;
-      rec.gc.v_geom[s] = v.geom;
-      rec.gc.v_dist[s] = v.dist;
-      rec.gc.v_u_traj[s] = v.u_traj;
-      rec.gc.v_u_cur[s] = v.u_cur;
-      rec.gc.a_pick[s] = a.pick;
-      rec.gc.a_geom[s] = a.geom;
-      rec.gc.a_dist[s] = a.dist;
-      rec.gc.a_u_traj[s] = a.u_traj;
-      rec.gc.a_u_cur[s] = a.u_cur;
-    }
+    store_draw_record(rec.gc, s, pick, v, a);
     }  // own
   }
   __syncthreads();
@@ -475,15 +436,7 @@ __device__ inline HgcPick hgc_chain(const ogbx_gc_buffer& buf, const ogbx_gc_con
   const int64_t a_rand = cfg.actor_cur_is_one ? 0 : rand_goal_of(buf, a.pick);
   if (hc.has_low_value_goals && !cfg.value_cur_is_one) l_rand = rand_goal_of(buf, l.pick);
   const int64_t next = idx + 1 < buf.num_rows ? idx + 1 : buf.num_rows - 1;
-  const double uvg = u01_from(w1.z, w1.w), uag = u01_from(w2.x, w2.y);
-  v.geom = cfg.value_geom_sample ? geometric_from(uvg, v_log_q) : 0;
-  a.geom = cfg.actor_geom_sample ? geometric_from(uag, a_log_q) : 0;
-  v.dist = uvg;
-  a.dist = uag;
-  v.u_traj = u01_from(w2.z, w2.w);
-  v.u_cur = u01_from(w3.x, w3.y);
-  a.u_traj = u01_from(w3.z, w3.w);
-  a.u_cur = u01_from(w4.x, w4.y);
+  goal_side_draws<false>(ogbx_gc_draws{}, cfg, 0, w1, w2, w3, w4, v_log_q, a_log_q, v, a);
   const int64_t hvg = sample_goal(idx, fin, v, v_rand, cfg.value_p_curgoal, cfg.value_traj_thresh,
                                   cfg.value_geom_sample, cfg.value_cur_is_one);
   const int64_t hag = sample_goal(idx, fin, a, a_rand, cfg.actor_p_curgoal, cfg.actor_traj_thresh,
@@ -775,9 +728,10 @@ ogbx_status ogbx_gc_sample(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg,
   const char* who = "ogbx_gc_sample";
   OGBX_CHECK(buf && cfg && masks && rewards, OGBX_EINVAL, named(who, "null argument"));
   GcColumns cc{};
-  GC_TRY(check_columns(cols, num_cols, batch, num_batches, 3, who, &cc));
+  bool flat4;
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, 3, who, &cc, &flat4));
   GC_TRY(check_buffer(buf));
-  return launch_gc_sample(*buf, *cfg, gc_params(seed, *cfg, nullptr), cc, num_cols, flat4_columns(cc, num_cols),
+  return launch_gc_sample(*buf, *cfg, gc_params(seed, *cfg, nullptr), cc, num_cols, flat4,
                           batch * num_batches, call_index, draws ? *draws : ogbx_gc_draws{},
                           record ? *record : ogbx_gc_draw_record{},
                           {idxs_out, value_goal_out, actor_goal_out, masks, rewards}, (hipStream_t)stream);
@@ -792,10 +746,11 @@ ogbx_status ogbx_gc_sample_ahead(const ogbx_gc_buffer* buf, const ogbx_gc_config
   const char* who = "ogbx_gc_sample_ahead";
   OGBX_CHECK(buf && cfg && masks && rewards, OGBX_EINVAL, named(who, "null argument"));
   GcColumns cc{};
-  GC_TRY(check_columns(cols, num_cols, batch, num_batches, 3, who, &cc));
+  bool flat4;
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, 3, who, &cc, &flat4));
   GC_TRY(check_ahead(batch * num_batches, ahead_in, ahead_out, who));
   GC_TRY(check_buffer(buf));
-  return launch_gc_ahead(*buf, *cfg, gc_params(seed, *cfg, nullptr), cc, num_cols, flat4_columns(cc, num_cols),
+  return launch_gc_ahead(*buf, *cfg, gc_params(seed, *cfg, nullptr), cc, num_cols, flat4,
                          batch * num_batches, call_index, ahead_in, ahead_out,
                          {idxs_out, value_goal_out, actor_goal_out, masks, rewards}, (hipStream_t)stream);
 }
@@ -809,12 +764,13 @@ ogbx_status ogbx_hgc_sample(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg
   const char* who = "ogbx_hgc_sample";
   OGBX_CHECK(buf && cfg && hcfg && out, OGBX_EINVAL, named(who, "null argument"));
   GcColumns cc{};
+  bool flat4;
   GC_TRY(check_hgc_outputs(out, who));
   GC_TRY(check_hgc_config(hcfg, who));
-  GC_TRY(check_columns(cols, num_cols, batch, num_batches, kHgcSel - 1, who, &cc));
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, kHgcSel - 1, who, &cc, &flat4));
   GC_TRY(check_buffer(buf));
   return launch_hgc_sample(*buf, *cfg, *hcfg, gc_params(seed, *cfg, hcfg), cc, num_cols,
-                           flat4_columns(cc, num_cols), batch * num_batches, call_index,
+                           flat4, batch * num_batches, call_index,
                            draws ? *draws : ogbx_hgc_draws{}, record ? *record : ogbx_hgc_draw_record{}, *out,
                            (hipStream_t)stream);
 }
@@ -827,13 +783,14 @@ ogbx_status ogbx_hgc_sample_ahead(const ogbx_gc_buffer* buf, const ogbx_gc_confi
   const char* who = "ogbx_hgc_sample_ahead";
   OGBX_CHECK(buf && cfg && hcfg && out, OGBX_EINVAL, named(who, "null argument"));
   GcColumns cc{};
+  bool flat4;
   GC_TRY(check_hgc_outputs(out, who));
   GC_TRY(check_hgc_config(hcfg, who));
-  GC_TRY(check_columns(cols, num_cols, batch, num_batches, kHgcSel - 1, who, &cc));
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, kHgcSel - 1, who, &cc, &flat4));
   GC_TRY(check_ahead(batch * num_batches, ahead_in, ahead_out, who));
   GC_TRY(check_buffer(buf));
   return launch_hgc_ahead(*buf, *cfg, *hcfg, gc_params(seed, *cfg, hcfg), cc, num_cols,
-                          flat4_columns(cc, num_cols), batch * num_batches, call_index, ahead_in, ahead_out, *out,
+                          flat4, batch * num_batches, call_index, ahead_in, ahead_out, *out,
                           (hipStream_t)stream);
 }
 
@@ -925,7 +882,7 @@ ogbx_status ogbx_gc_plan_set_batch(ogbx_gc_plan_t p, int32_t slot, const ogbx_gc
   OGBX_CHECK(p, OGBX_EINVAL, "null plan");
   OGBX_CHECK(slot >= 0 && slot < OGBX_GC_PLAN_SLOTS, OGBX_EINVAL, named(who, "slot out of range"));
   PlanBatch b;
-  GC_TRY(check_columns(cols, num_cols, batch, num_batches, p->hgc ? kHgcSel - 1 : 3, who, &b.cc));
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, p->hgc ? kHgcSel - 1 : 3, who, &b.cc, &b.flat4));
   if (p->hgc)
     GC_TRY(check_hgc_outputs(hgc_out, who));
   else
@@ -934,7 +891,6 @@ ogbx_status ogbx_gc_plan_set_batch(ogbx_gc_plan_t p, int32_t slot, const ogbx_gc
   b.total = batch * num_batches;
   b.out = {idxs_out, value_goal_out, actor_goal_out, masks, rewards};
   if (hgc_out) b.hout = *hgc_out;
-  b.flat4 = flat4_columns(b.cc, num_cols);
   b.small = num_cols <= kGcSmallCols;
   for (int i = 0; i < kGcSmallCols && i < num_cols; ++i) b.cs.c[i] = b.cc.c[i];
   b.set = true;

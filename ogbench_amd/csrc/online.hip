@@ -21,7 +21,9 @@
 // its episode's end comes from ep_seq / cur_seq / ep_end, the goals are drawn
 // on flat indices by sample_goal, and each selector is mapped to its physical
 // row.  The ring's view, the row map and the end lookup live in
-// online_device.h, shared with online_hgc_sample_kernel (online_hgc.hip).
+// online_device.h, shared with online_hgc_sample_kernel (online_hgc.hip); the
+// goal draws besides the picks, the draw record and the host's column check
+// are gc_device.h's (goal_side_draws, store_draw_record, check_gather_columns).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -120,15 +122,7 @@ __global__ void __launch_bounds__(256) online_gc_sample_kernel(
     split_flat(ring, idx, &e, &k);
     const int64_t prow = phys_row(ring, e, k);
     const int64_t final_idx = episode_end_flat(ring, episode_seq(ring, e, prow), idx, e, k);
-    const double uvg = u01_from(w1.z, w1.w), uag = u01_from(w2.x, w2.y);
-    v.geom = (kInj && dr.v_geom) ? dr.v_geom[s] : (cfg.value_geom_sample ? geometric_from(uvg, v_log_q) : 0);
-    a.geom = (kInj && dr.a_geom) ? dr.a_geom[s] : (cfg.actor_geom_sample ? geometric_from(uag, a_log_q) : 0);
-    v.dist = (kInj && dr.v_dist) ? dr.v_dist[s] : uvg;
-    a.dist = (kInj && dr.a_dist) ? dr.a_dist[s] : uag;
-    v.u_traj = (kInj && dr.v_u_traj) ? dr.v_u_traj[s] : u01_from(w2.z, w2.w);
-    v.u_cur = (kInj && dr.v_u_cur) ? dr.v_u_cur[s] : u01_from(w3.x, w3.y);
-    a.u_traj = (kInj && dr.a_u_traj) ? dr.a_u_traj[s] : u01_from(w3.z, w3.w);
-    a.u_cur = (kInj && dr.a_u_cur) ? dr.a_u_cur[s] : u01_from(w4.x, w4.y);
+    goal_side_draws<kInj>(dr, cfg, s, w1, w2, w3, w4, v_log_q, a_log_q, v, a);
     int64_t vg = sample_goal(idx, final_idx, v, v.pick, cfg.value_p_curgoal, cfg.value_traj_thresh,
                              cfg.value_geom_sample, cfg.value_cur_is_one);
     int64_t ag = sample_goal(idx, final_idx, a, a.pick, cfg.actor_p_curgoal, cfg.actor_traj_thresh,
@@ -148,19 +142,7 @@ __global__ void __launch_bounds__(256) online_gc_sample_kernel(
       const double succ = idx == vg ? 1.0 : 0.0;
       masks[s] = 1.0 - succ;
       rewards[s] = succ - (cfg.gc_negative ? 1.0 : 0.0);
-      if (rec.pick) {
-        rec.pick[s] = pick;
-        rec.v_pick[s] = v.pick;
-        rec.v_geom[s] = v.geom;
-        rec.v_dist[s] = v.dist;
-        rec.v_u_traj[s] = v.u_traj;
-        rec.v_u_cur[s] = v.u_cur;
-        rec.a_pick[s] = a.pick;
-        rec.a_geom[s] = a.geom;
-        rec.a_dist[s] = a.dist;
-        rec.a_u_traj[s] = a.u_traj;
-        rec.a_u_cur[s] = a.u_cur;
-      }
+      store_draw_record(rec, s, pick, v, a);
     }
   }
   __syncthreads();
@@ -234,18 +216,9 @@ ogbx_status ogbx_online_gc_sample(const ogbx_online_ring* ring, const ogbx_gc_co
   OGBX_CHECK(num_cols >= 0 && num_cols <= OGBX_REPLAY_MAX_COLS, OGBX_EINVAL, who + "0 to 16 columns");
   OGBX_CHECK(num_cols == 0 || batch->cols, OGBX_EINVAL, who + "null columns");
   GcColumnsSmall cc{};
-  bool flat4 = true;
-  for (int i = 0; i < num_cols; ++i) {
-    const ogbx_gc_column& c = batch->cols[i];
-    OGBX_CHECK(c.src && c.dst, OGBX_EINVAL, who + "null column pointer");
-    OGBX_CHECK(c.row_bytes > 0 && (c.select == 0 || c.select == 2 || c.select == 3), OGBX_EINVAL,
-               who + "bad column descriptor");
-    OGBX_CHECK(c.src_stride == 0 || c.src_stride >= c.row_bytes, OGBX_EINVAL, who + "src_stride below row_bytes");
-    cc.c[i] = c;
-    // copy_tile's per-wave job copy: 4-byte granular, aligned rows of <= 128 words
-    flat4 = flat4 && c.row_bytes % 4 == 0 && c.row_bytes <= 512 &&
-            ((uintptr_t)c.src | (uintptr_t)c.dst | (uintptr_t)c.src_stride) % 4 == 0;
-  }
+  bool flat4;
+  // the row itself and the two goals: a ring stores its own next_observations
+  GC_TRY(check_gather_columns<true>(batch->cols, num_cols, 0b1101u, "ogbx_online_gc_sample", &cc, &flat4));
   const int64_t total = batch->total;
   const int64_t tile = gc_tile(total);
   const int64_t blocks = (total + tile - 1) / tile;

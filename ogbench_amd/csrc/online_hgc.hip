@@ -11,7 +11,9 @@
 // online_hgc_sample_kernel: hgc_sample_kernel's tile structure, slot layout and
 // ten selectors (gcsample.hip, gc_device.h, gc_select.h) with the index loads
 // replaced by the ring's (online_device.h), as online_gc_sample_kernel does it
-// for the two GC goals.  All goal and subgoal arithmetic runs on flat indices;
+// for the two GC goals, with the same pieces of gc_device.h (goal_side_draws,
+// store_draw_record, check_gather_columns); the l_* draws and their record are
+// written here.  All goal and subgoal arithmetic runs on flat indices;
 // the five derived selectors stay in [idx, fin], i.e. in the sample's env, so
 // their physical rows need no second division.
 #include <hip/hip_runtime.h>
@@ -95,15 +97,7 @@ __global__ void __launch_bounds__(256) online_hgc_sample_kernel(
     GoalDraws v, a, l{};
     v.pick = (kInj && g.v_pick) ? clamp_row(g.v_pick[s], npick) : (int64_t)bounded64(w0.z, w0.w, (uint64_t)npick);
     a.pick = (kInj && g.a_pick) ? clamp_row(g.a_pick[s], npick) : (int64_t)bounded64(w1.x, w1.y, (uint64_t)npick);
-    const double uvg = u01_from(w1.z, w1.w), uag = u01_from(w2.x, w2.y);
-    v.geom = (kInj && g.v_geom) ? g.v_geom[s] : (cfg.value_geom_sample ? geometric_from(uvg, v_log_q) : 0);
-    a.geom = (kInj && g.a_geom) ? g.a_geom[s] : (cfg.actor_geom_sample ? geometric_from(uag, a_log_q) : 0);
-    v.dist = (kInj && g.v_dist) ? g.v_dist[s] : uvg;
-    a.dist = (kInj && g.a_dist) ? g.a_dist[s] : uag;
-    v.u_traj = (kInj && g.v_u_traj) ? g.v_u_traj[s] : u01_from(w2.z, w2.w);
-    v.u_cur = (kInj && g.v_u_cur) ? g.v_u_cur[s] : u01_from(w3.x, w3.y);
-    a.u_traj = (kInj && g.a_u_traj) ? g.a_u_traj[s] : u01_from(w3.z, w3.w);
-    a.u_cur = (kInj && g.a_u_cur) ? g.a_u_cur[s] : u01_from(w4.x, w4.y);
+    goal_side_draws<kInj>(g, cfg, s, w1, w2, w3, w4, v_log_q, a_log_q, v, a);
     if (hc.has_low_value_goals) {
       l.pick = (kInj && dr.l_pick) ? clamp_row(dr.l_pick[s], npick) : (int64_t)bounded64(w5.x, w5.y, (uint64_t)npick);
       l.geom = (kInj && dr.l_geom) ? dr.l_geom[s] : geometric_from(u01_from(w5.z, w5.w), l_log_q);
@@ -115,19 +109,7 @@ __global__ void __launch_bounds__(256) online_hgc_sample_kernel(
     const int64_t fin = episode_end_flat(ring, eps, idx, e, k);
     // the draw record (the kInj instance alone: a recording call launches it)
     if (kInj && own) {
-      if (rec.gc.pick) {
-        rec.gc.pick[s] = pick;
-        rec.gc.v_pick[s] = v.pick;
-        rec.gc.v_geom[s] = v.geom;
-        rec.gc.v_dist[s] = v.dist;
-        rec.gc.v_u_traj[s] = v.u_traj;
-        rec.gc.v_u_cur[s] = v.u_cur;
-        rec.gc.a_pick[s] = a.pick;
-        rec.gc.a_geom[s] = a.geom;
-        rec.gc.a_dist[s] = a.dist;
-        rec.gc.a_u_traj[s] = a.u_traj;
-        rec.gc.a_u_cur[s] = a.u_cur;
-      }
+      store_draw_record(rec.gc, s, pick, v, a);
       if (rec.l_pick && hc.has_low_value_goals) {
         rec.l_pick[s] = l.pick;
         rec.l_geom[s] = l.geom;
@@ -240,17 +222,10 @@ ogbx_status ogbx_online_hgc_sample(const ogbx_online_ring* ring, const ogbx_gc_c
              OGBX_EINVAL, who + "missing scalar output");
   OGBX_CHECK(num_cols >= 0 && num_cols <= kGcMaxCols, OGBX_EINVAL, who + "0 to 32 columns");
   OGBX_CHECK(num_cols == 0 || cols, OGBX_EINVAL, who + "null columns");
-  bool flat4 = true;
-  for (int i = 0; i < num_cols; ++i) {
-    const ogbx_gc_column& c = cols[i];
-    OGBX_CHECK(c.src && c.dst, OGBX_EINVAL, who + "null column pointer");
-    OGBX_CHECK(c.row_bytes > 0 && c.select >= 0 && c.select < kHgcSel && c.select != 1, OGBX_EINVAL,
-               who + "bad column descriptor");
-    OGBX_CHECK(c.src_stride == 0 || c.src_stride >= c.row_bytes, OGBX_EINVAL, who + "src_stride below row_bytes");
-    // copy_tile's per-wave job copy: 4-byte granular, aligned rows of <= 128 words
-    flat4 = flat4 && c.row_bytes % 4 == 0 && c.row_bytes <= 512 &&
-            ((uintptr_t)c.src | (uintptr_t)c.dst | (uintptr_t)c.src_stride) % 4 == 0;
-  }
+  bool flat4;
+  // every selector but next (1); the table is copied by launch_online_hgc, at the size it launches with
+  GC_TRY(check_gather_columns<true>(cols, num_cols, selects_up_to(kHgcSel - 1) & ~0b10u, "ogbx_online_hgc_sample",
+                                    (GcColumns*)nullptr, &flat4));
   const int64_t tile = gc_tile(total);
   OGBX_CHECK((total + tile - 1) / tile <= 0x7fffffffll, OGBX_EINVAL, who + "too many samples for one launch");
 

@@ -17,7 +17,8 @@
 //
 // replay_sample_kernel: gc_sample_kernel's tile structure (gc_device.h) with
 // one Philox call per sample and two selectors, idx and next; size comes from
-// the header.
+// the header.  Its column table is checked by gc_device.h's
+// check_gather_columns, as the ring samplers' are.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -239,17 +240,8 @@ ogbx_status ogbx_replay_sample(const int64_t* header, int32_t parity, int64_t ma
   OGBX_CHECK(max_size > 0 && total > 0, OGBX_EINVAL, who + "max_size and total must be > 0");
   OGBX_CHECK(num_cols >= 1 && num_cols <= OGBX_REPLAY_MAX_COLS, OGBX_EINVAL, who + "1 to 16 columns");
   GcColumnsSmall cc{};
-  bool flat4 = true;
-  for (int i = 0; i < num_cols; ++i) {
-    const ogbx_gc_column& c = cols[i];
-    OGBX_CHECK(c.src && c.dst, OGBX_EINVAL, who + "null column pointer");
-    OGBX_CHECK(c.row_bytes > 0 && (c.select == 0 || c.select == 1), OGBX_EINVAL, who + "bad column descriptor");
-    OGBX_CHECK(c.src_stride == 0 || c.src_stride >= c.row_bytes, OGBX_EINVAL, who + "src_stride below row_bytes");
-    cc.c[i] = c;
-    // copy_tile's per-wave job copy: 4-byte granular, aligned rows of <= 128 words
-    flat4 = flat4 && c.row_bytes % 4 == 0 && c.row_bytes <= 512 &&
-            ((uintptr_t)c.src | (uintptr_t)c.dst | (uintptr_t)c.src_stride) % 4 == 0;
-  }
+  bool flat4;
+  GC_TRY(check_gather_columns<true>(cols, num_cols, 0b11u, "ogbx_replay_sample", &cc, &flat4));  // idx, next
   const int64_t tile = gc_tile(total);
   const int64_t blocks = (total + tile - 1) / tile;
   OGBX_CHECK(blocks <= 0x7fffffffll, OGBX_EINVAL, who + "too many samples for one launch");

@@ -70,15 +70,7 @@ __global__ void __launch_bounds__(256) trl_sample_kernel(
     const int64_t v_rand = cfg.value_cur_is_one ? 0 : rand_goal_of(buf, v.pick);
     const int64_t a_rand = cfg.actor_cur_is_one ? 0 : rand_goal_of(buf, a.pick);
     const int64_t next = idx + 1 < buf.num_rows ? idx + 1 : buf.num_rows - 1;
-    const double uvg = u01_from(w1.z, w1.w), uag = u01_from(w2.x, w2.y);
-    v.geom = (kInj && dr.v_geom) ? dr.v_geom[s] : (cfg.value_geom_sample ? geometric_from(uvg, v_log_q) : 0);
-    a.geom = (kInj && dr.a_geom) ? dr.a_geom[s] : (cfg.actor_geom_sample ? geometric_from(uag, a_log_q) : 0);
-    v.dist = (kInj && dr.v_dist) ? dr.v_dist[s] : uvg;
-    a.dist = (kInj && dr.a_dist) ? dr.a_dist[s] : uag;
-    v.u_traj = (kInj && dr.v_u_traj) ? dr.v_u_traj[s] : u01_from(w2.z, w2.w);
-    v.u_cur = (kInj && dr.v_u_cur) ? dr.v_u_cur[s] : u01_from(w3.x, w3.y);
-    a.u_traj = (kInj && dr.a_u_traj) ? dr.a_u_traj[s] : u01_from(w3.z, w3.w);
-    a.u_cur = (kInj && dr.a_u_cur) ? dr.a_u_cur[s] : u01_from(w4.x, w4.y);
+    goal_side_draws<kInj>(dr, cfg, s, w1, w2, w3, w4, v_log_q, a_log_q, v, a);
     const int64_t vg = sample_goal(idx, final_idx, v, v_rand, cfg.value_p_curgoal,
                                    cfg.value_traj_thresh, cfg.value_geom_sample, cfg.value_cur_is_one);
     const int64_t ag = sample_goal(idx, final_idx, a, a_rand, cfg.actor_p_curgoal,
@@ -116,19 +108,7 @@ __global__ void __launch_bounds__(256) trl_sample_kernel(
     if (o.masks) o.masks[s] = 1.0 - succ;
     if (o.rewards) o.rewards[s] = succ - (cfg.gc_negative ? 1.0 : 0.0);
     if (mid_rec) mid_rec[s] = mid;
-    if (rec.pick) {
-      rec.pick[s] = pick;
-      rec.v_pick[s] = v.pick;
-      rec.v_geom[s] = v.geom;
-      rec.v_dist[s] = v.dist;
-      rec.v_u_traj[s] = v.u_traj;
-      rec.v_u_cur[s] = v.u_cur;
-      rec.a_pick[s] = a.pick;
-      rec.a_geom[s] = a.geom;
-      rec.a_dist[s] = a.dist;
-      rec.a_u_traj[s] = a.u_traj;
-      rec.a_u_cur[s] = a.u_cur;
-    }
+    store_draw_record(rec, s, pick, v, a);
     }  // own
   }
   __syncthreads();
@@ -166,7 +146,8 @@ ogbx_status ogbx_trl_sample(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg
   const char* who = "ogbx_trl_sample";
   OGBX_CHECK(buf && cfg && out && (cols || num_cols == 0), OGBX_EINVAL, named(who, "null argument"));
   GcColumns cc{};
-  GC_TRY(check_columns(cols, num_cols, batch, num_batches, OGBX_TRL_SELECT_MIDPOINT, who, &cc));
+  bool flat4;
+  GC_TRY(check_columns(cols, num_cols, batch, num_batches, OGBX_TRL_SELECT_MIDPOINT, who, &cc, &flat4));
   GC_TRY(check_buffer(buf));
   const ogbx_gc_draws dr = draws ? *draws : ogbx_gc_draws{};
   const ogbx_gc_draw_record rec = record ? *record : ogbx_gc_draw_record{};
@@ -191,11 +172,10 @@ ogbx_status ogbx_trl_sample(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg
   const GcParams pr = gc_params(seed, *cfg, nullptr);  // the GC stream tag: same words as ogbx_gc_sample
   const int64_t total = batch * num_batches;
   const int64_t tile = gc_tile(total), blocks = (total + tile - 1) / tile;
-  const bool flat4 = tile <= 4 && flat4_columns(cc, num_cols);
   const auto kern = (any_draw(dr) || midpoint) ? trl_sample_kernel<true> : trl_sample_kernel<false>;
   hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, *buf, *cfg, cc, num_cols,
                      total, (int)tile, dr, midpoint, pr.k0, pr.k1, (uint32_t)call_index,
-                     (uint32_t)(call_index >> 32), pr.v_log_q, pr.a_log_q, *out, rec, midpoint_record, flat4);
+                     (uint32_t)(call_index >> 32), pr.v_log_q, pr.a_log_q, *out, rec, midpoint_record, tile <= 4 && flat4);
   OGBX_LAUNCHED("trl_sample_kernel");
   return OGBX_OK;
 }

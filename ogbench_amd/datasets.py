@@ -1295,6 +1295,55 @@ def _bind_hgc():
     return L
 
 
+# What HGCDataset.sample returns after the dataset's own keys, in the reference's
+# order (datasets.py:496-643): (key, source, select) is a gathered column, its
+# source 'goal' being ``oracle_reps`` where the data has it and ``observations``
+# otherwise (datasets.py:348-357); (key, 'scalar', dtype) a per-sample output of
+# the kernel; (key, 'alias', other) the same tensor as ``other``.
+_HGC_LAYOUT = (
+    ('high_value_reps', 'alias', 'observations'),
+    ('high_value_goals', 'goal', 2),
+    ('high_value_actions', 'goal', 4),
+    ('high_value_next_observations', 'observations', 4),
+    ('high_value_offsets', 'scalar', 'int64'),
+    ('high_value_subgoal_steps', 'scalar', 'int64'),
+    ('high_value_masks', 'scalar', 'float64'),
+    ('high_value_rewards', 'scalar', 'float64'),
+    ('low_value_next_observations', 'observations', 5),
+    ('low_value_subgoal_steps', 'scalar', 'int64'),
+    ('low_value_masks', 'scalar', 'float64'),
+    ('low_value_rewards', 'scalar', 'float64'),
+    ('low_value_goals', 'goal', 6),  # with low_discount only
+    ('value_goals', 'alias', 'high_value_goals'),
+    ('masks', 'scalar', 'float64'),
+    ('rewards', 'scalar', 'float64'),
+    ('high_actor_goals', 'goal', 3),
+    ('high_actor_actions', 'goal', 7),
+    ('high_actor_next_observations', 'observations', 7),
+    ('high_actor_targets', 'alias', 'high_actor_actions'),
+    ('low_actor_goals', 'goal', 8),
+    ('low_actor_goal_observations', 'observations', 8),
+    ('low_actor_next_observations', 'observations', 9),
+)
+
+
+def _hgc_outputs(out, total, goal_src, has_low, device, own_reps=False):
+    """Walk ``_HGC_LAYOUT`` over ``out``, which holds the data's own keys:
+    aliases and scalar outputs are added here, and every gathered column is
+    yielded as (key, src_key, select) for the caller to make ``out[key]``
+    before the walk goes on.  own_reps: the caller has put
+    ``high_value_reps``, the first key, there already (a visual batch, where it
+    is no alias)."""
+    torch = _torch()
+    for key, what, arg in _HGC_LAYOUT[int(own_reps):]:
+        if what == 'alias':
+            out[key] = out[arg]
+        elif what == 'scalar':
+            out[key] = torch.empty(total, dtype=getattr(torch, arg), device=device)
+        elif has_low or key != 'low_value_goals':
+            yield key, (goal_src if what == 'goal' else what), arg
+
+
 def _subgoal_tables(discount, K, gc_negative, device):
     """masks / rewards of HGCDataset.sample as functions of the clipped subgoal
     step count s in [0, K] (datasets.py:533-541, 550-556), computed with the
@@ -1373,38 +1422,16 @@ class HGCDataset(GCDataset):
             cols.append(self._column(src_key, dst, select))
             return dst
 
-        def scalar(dtype):
-            return torch.empty(total, dtype=dtype, device=self.device)
-
         for k in ds.keys():
             out[k] = col(k, 0, k)
         if 'next_observations' not in ds:
             out['next_observations'] = col('observations', 1, 'next_observations')
-        i64, f64 = torch.int64, torch.float64
-        # a visual batch's observations may be cropped; high_value_reps never is
-        out['high_value_reps'] = col('observations', 0, 'high_value_reps') if vcols is not None \
-            else out['observations']
-        out['high_value_goals'] = col(goal_src, 2, 'high_value_goals')
-        out['high_value_actions'] = col(goal_src, 4, 'high_value_actions')
-        out['high_value_next_observations'] = col('observations', 4, 'high_value_next_observations')
-        for k, dt in (('high_value_offsets', i64), ('high_value_subgoal_steps', i64), ('high_value_masks', f64),
-                      ('high_value_rewards', f64)):
-            out[k] = scalar(dt)
-        out['low_value_next_observations'] = col('observations', 5, 'low_value_next_observations')
-        for k, dt in (('low_value_subgoal_steps', i64), ('low_value_masks', f64), ('low_value_rewards', f64)):
-            out[k] = scalar(dt)
-        if self._has_low:
-            out['low_value_goals'] = col(goal_src, 6, 'low_value_goals')
-        out['value_goals'] = out['high_value_goals']
-        out['masks'] = scalar(f64)
-        out['rewards'] = scalar(f64)
-        out['high_actor_goals'] = col(goal_src, 3, 'high_actor_goals')
-        out['high_actor_actions'] = col(goal_src, 7, 'high_actor_actions')
-        out['high_actor_next_observations'] = col('observations', 7, 'high_actor_next_observations')
-        out['high_actor_targets'] = out['high_actor_actions']
-        out['low_actor_goals'] = col(goal_src, 8, 'low_actor_goals')
-        out['low_actor_goal_observations'] = col('observations', 8, 'low_actor_goal_observations')
-        out['low_actor_next_observations'] = col('observations', 9, 'low_actor_next_observations')
+        if vcols is not None:
+            # a visual batch's observations may be cropped; high_value_reps never is
+            out['high_value_reps'] = col('observations', 0, 'high_value_reps')
+        for key, src_key, select in _hgc_outputs(out, total, goal_src, self._has_low, self.device,
+                                                 own_reps=vcols is not None):
+            out[key] = col(src_key, select, key)
         return out, cols
 
     # sample() is GCDataset's; what differs for the hierarchical sampler:
@@ -1687,7 +1714,119 @@ def _replay_dtypes():
     return {torch.bool: 0, torch.uint8: 1, torch.int32: 2, torch.int64: 3, torch.float32: 4, torch.float64: 5}
 
 
-class ReplayBuffer(Dataset):
+class _BufferHost:
+    """The host side that ``ReplayBuffer`` and the ring buffers share (each is
+    also a ``Dataset`` of device columns): staging of what an insert takes, the
+    cached insert descriptors, the descriptor of a gathered column and the
+    ``out=`` cache."""
+
+    _next_seed = GCDataset._next_seed
+
+    def _init_host(self, seed):
+        self._L = _bind()
+        self._dtype_code = _replay_dtypes()
+        self._seed = int(seed) if seed is not None else None
+        self._calls = 0
+        self._ins_cache = {}
+        self._out_cache = {}
+        self._out_gen = self._gen
+        self._dev_idx = self.device.index
+        torch = _torch()
+        self._raw_stream = torch._C._cuda_getCurrentRawStream  # hipStream_t of the current stream, as an int
+        self._new = torch.empty  # a new batch allocates a tensor per key
+
+    def _source(self, key, v, n):
+        """One leaf of an insert as a contiguous device tensor of n rows."""
+        torch = _torch()
+        if not isinstance(v, torch.Tensor):
+            v = torch.as_tensor(np.ascontiguousarray(v))
+        if v.device != self.device:
+            v = v.to(self.device)
+        if v.dtype not in self._dtype_code:
+            raise ValueError(f'{key!r}: unsupported source dtype {v.dtype}')
+        col = self[key]
+        if v.dim() == 0 or v.shape[0] != n or tuple(v.shape[1:]) != tuple(col.shape[1:]):
+            raise ValueError(f'{key!r}: expected shape {(n,) + tuple(col.shape[1:])}, got {tuple(v.shape)}')
+        return v if v.is_contiguous() else v.contiguous()
+
+    def _mask(self, name, m, n):
+        torch = _torch()
+        if m is None:
+            return None
+        if not isinstance(m, torch.Tensor):
+            m = torch.as_tensor(np.ascontiguousarray(m))
+        if m.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'{name} must be bool or uint8, got {m.dtype}')
+        if m.device != self.device:
+            m = m.to(self.device)
+        if m.dim() != 1 or not m.is_contiguous():
+            m = m.reshape(-1).contiguous()
+        if m.shape[0] != n:
+            raise ValueError(f'{name} must have {n} entries, got {m.shape[0]}')
+        return m  # the kernel reads bytes; torch's bool bytes are 0 / 1
+
+    def _check_keys(self, keys):
+        if set(keys) != set(self.keys()):
+            raise ValueError(f'the transition has keys {sorted(keys)}, the buffer {sorted(self.keys())}')
+
+    def _column_of(self, key, rows):
+        """The buffer's column ``key``, still the ``rows`` contiguous rows on
+        the buffer's device that the kernels index."""
+        col = self[key]
+        if len(col) != rows or not col.is_contiguous() or col.device != self.device:
+            raise ValueError(f'buffer column {key!r} was replaced by one of another length, layout or device')
+        return col
+
+    def _insert_columns(self, specs, rows, call_key, max_cols=None):
+        """The ``ReplayInsertColumn`` array of an insert into columns of
+        ``rows`` rows.  specs: (key, src, alt or None, op) per column, staged
+        by ``_source``.  Cached under what the descriptors depend on: the
+        sources' addresses and dtypes, the buffer's generation and
+        ``call_key``, the call's other pointers."""
+        key = call_key + (self._gen,) + tuple(
+            (k, s.data_ptr(), s.dtype, a.data_ptr() if a is not None else 0, op) for k, s, a, op in specs)
+        arr = self._ins_cache.get(key)
+        if arr is None:
+            code = self._dtype_code
+            cols = []
+            for k, s, a, op in specs:
+                col = self._column_of(k, rows)
+                if col.dtype not in code or col.dtype is _torch().bool:
+                    raise ValueError(f'{k!r}: unsupported column dtype {col.dtype}')
+                if a is not None and a.dtype != s.dtype:
+                    raise ValueError(f'{k!r}: the alternative source has dtype {a.dtype}, the source {s.dtype}')
+                row = col[0].numel() if col.dim() > 1 else 1
+                cols.append(ReplayInsertColumn(col.data_ptr(), s.data_ptr(), a.data_ptr() if a is not None else None,
+                                               row, code[s.dtype], code[col.dtype], op, 0))
+            if max_cols is not None and len(cols) > max_cols:
+                raise ValueError(f'at most {max_cols} columns per insert, got {len(cols)}')
+            arr = (ReplayInsertColumn * len(cols))(*cols)
+            if len(self._ins_cache) >= 8:
+                self._ins_cache.clear()
+            self._ins_cache[key] = arr
+        return arr
+
+    def _gather_column(self, src_key, B, select, rows):
+        """(destination of B rows, descriptor) of one gathered column."""
+        src = self[src_key]
+        if len(src) != rows or not src.is_contiguous() or src.device != self.device:
+            self._column_of(src_key, rows)  # raises: the column was replaced
+        dst = self._new((B,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
+        row_bytes = (src[0].numel() if src.dim() > 1 else 1) * src.element_size()
+        return dst, GcColumn(src.data_ptr(), dst.data_ptr(), row_bytes, select, 0)
+
+    # The out= cache: the last two batches that plain calls returned, by
+    # id(out), each with its shape and what a refill passes on; emptied when a
+    # column was replaced.  A steady refill is host-bound (DESIGN 4.11), so the
+    # lookup and the refill's one ctypes call stand in line in each sample(),
+    # not behind a call of their own; only a new batch comes through here.
+    def _out_remember(self, out, shape, held):
+        if len(self._out_cache) >= 2:
+            self._out_cache.clear()
+        self._out_cache[id(out)] = (out, shape, held)
+
+
+class ReplayBuffer(_BufferHost, Dataset):
     """Replay buffer on the device (reference: datasets.py:86-146; used by
     data_gen_scripts/main_sac.py:66-137): a ``Dataset`` whose rows are written
     by batched ring inserts and drawn uniformly from the rows held so far.
@@ -1787,22 +1926,12 @@ class ReplayBuffer(Dataset):
         if len(lens) != 1:
             raise ValueError(f'every column of a ReplayBuffer needs the same number of rows, got {sorted(lens)}')
         self.max_size = lens.pop()
-        self._L = _bind()
-        self._dtype_code = _replay_dtypes()
+        self._init_host(seed)
         self._hdr = torch.zeros(4, dtype=torch.int64, device=self.device)  # OGBX_REPLAY_HEADER_WORDS
         self._empty = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._parity = 0
         self._h_pointer = self._h_size = 0
         self._known = True
-        self._seed = int(seed) if seed is not None else None
-        self._calls = 0
-        self._ins_cache = {}
-        self._out_cache = {}
-        self._out_gen = self._gen
-        self._dev_idx = self.device.index
-        self._raw_stream = torch._C._cuda_getCurrentRawStream  # hipStream_t of the current stream, as an int
-
-    _next_seed = GCDataset._next_seed
 
     # ------------------------------------------------------------------ header
     def _set_header(self, pointer, size):
@@ -1855,36 +1984,6 @@ class ReplayBuffer(Dataset):
         return int(self._empty.item())
 
     # ------------------------------------------------------------------ inserts
-    def _source(self, key, v, n):
-        """One leaf of an insert as a contiguous device tensor of n rows."""
-        torch = _torch()
-        if not isinstance(v, torch.Tensor):
-            v = torch.as_tensor(np.ascontiguousarray(v))
-        if v.device != self.device:
-            v = v.to(self.device)
-        if v.dtype not in self._dtype_code:
-            raise ValueError(f'{key!r}: unsupported source dtype {v.dtype}')
-        col = self[key]
-        if v.dim() == 0 or v.shape[0] != n or tuple(v.shape[1:]) != tuple(col.shape[1:]):
-            raise ValueError(f'{key!r}: expected shape {(n,) + tuple(col.shape[1:])}, got {tuple(v.shape)}')
-        return v if v.is_contiguous() else v.contiguous()
-
-    def _mask(self, name, m, n):
-        torch = _torch()
-        if m is None:
-            return None
-        if not isinstance(m, torch.Tensor):
-            m = torch.as_tensor(np.ascontiguousarray(m))
-        if m.dtype not in (torch.bool, torch.uint8):
-            raise ValueError(f'{name} must be bool or uint8, got {m.dtype}')
-        if m.device != self.device:
-            m = m.to(self.device)
-        if m.dim() != 1 or not m.is_contiguous():
-            m = m.reshape(-1).contiguous()
-        if m.shape[0] != n:
-            raise ValueError(f'{name} must have {n} entries, got {m.shape[0]}')
-        return m  # the kernel reads bytes; torch's bool bytes are 0 / 1
-
     def _insert(self, specs, n, keep, alt_select):
         """specs: (key, src, alt or None, op) per column, already staged by
         ``_source``.  One launch; the host mirror follows when no mask."""
@@ -1895,30 +1994,10 @@ class ReplayBuffer(Dataset):
             return
         if self._known and self._h_pointer >= self.max_size:
             raise IndexError(f'index {self._h_pointer} is out of bounds for axis 0 with size {self.max_size}')
-        key = (n, keep.data_ptr() if keep is not None else 0, alt_select.data_ptr() if alt_select is not None else 0,
-               self._gen) + tuple((k, s.data_ptr(), s.dtype, a.data_ptr() if a is not None else 0, op)
-                                  for k, s, a, op in specs)
-        arr = self._ins_cache.get(key)
-        if arr is None:
-            code = self._dtype_code
-            cols = []
-            for k, s, a, op in specs:
-                col = self[k]
-                if len(col) != self.max_size or not col.is_contiguous() or col.device != self.device:
-                    raise ValueError(f'buffer column {k!r} was replaced by one of another length, layout or device')
-                if col.dtype not in code or col.dtype is _torch().bool:
-                    raise ValueError(f'{k!r}: unsupported column dtype {col.dtype}')
-                if a is not None and a.dtype != s.dtype:
-                    raise ValueError(f'{k!r}: the alternative source has dtype {a.dtype}, the source {s.dtype}')
-                row = col[0].numel() if col.dim() > 1 else 1
-                cols.append(ReplayInsertColumn(col.data_ptr(), s.data_ptr(), a.data_ptr() if a is not None else None,
-                                               row, code[s.dtype], code[col.dtype], op, 0))
-            if len(cols) > REPLAY_MAX_COLS:
-                raise ValueError(f'at most {REPLAY_MAX_COLS} columns per insert, got {len(cols)}')
-            arr = (ReplayInsertColumn * len(cols))(*cols)
-            if len(self._ins_cache) >= 8:
-                self._ins_cache.clear()
-            self._ins_cache[key] = arr
+        arr = self._insert_columns(
+            specs, self.max_size,
+            (n, keep.data_ptr() if keep is not None else 0, alt_select.data_ptr() if alt_select is not None else 0),
+            max_cols=REPLAY_MAX_COLS)
         st = self._L.ogbx_replay_insert(self._hdr.data_ptr(), self._parity, self.max_size, arr, len(arr), n,
                                         _lib.ptr(keep), _lib.ptr(alt_select), self._raw_stream(self._dev_idx))
         if st:
@@ -1937,10 +2016,6 @@ class ReplayBuffer(Dataset):
         end = pointer + m
         top = end if end < max_size else (max_size - 1 if pointer < max_size - 1 else m - 1)
         return end % max_size, max(size, top)
-
-    def _check_keys(self, keys):
-        if set(keys) != set(self.keys()):
-            raise ValueError(f'the transition has keys {sorted(keys)}, the buffer {sorted(self.keys())}')
 
     def add_transitions(self, batch, keep=None):
         """Insert one row per env: every leaf of ``batch`` has a leading N.
@@ -1994,19 +2069,13 @@ class ReplayBuffer(Dataset):
         torch = _torch()
         out, cols = {}, []
 
-        def add(src_key, dst_key, select):
-            src = self[src_key]
-            if len(src) != self.max_size or not src.is_contiguous() or src.device != self.device:
-                raise ValueError(f'buffer column {src_key!r} was replaced by one of another length, layout or device')
-            dst = torch.empty((B,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
-            out[dst_key] = dst
-            row_bytes = (src[0].numel() if src.dim() > 1 else 1) * src.element_size()
-            cols.append(GcColumn(src.data_ptr(), dst.data_ptr(), row_bytes, select, 0))
-
+        gather, rows = self._gather_column, self.max_size
         for k in self.keys():
-            add(k, k, 0)
+            out[k], col = gather(k, B, 0, rows)
+            cols.append(col)
         if 'next_observations' not in self:
-            add('observations', 'next_observations', 1)  # datasets.py:81-82
+            out['next_observations'], col = gather('observations', B, 1, rows)  # datasets.py:81-82
+            cols.append(col)
         if len(cols) > REPLAY_MAX_COLS:
             raise ValueError(f'at most {REPLAY_MAX_COLS} columns per sample, got {len(cols)}')
         idx = torch.empty(B, dtype=torch.int64, device=self.device) if record_idxs else None
@@ -2044,9 +2113,7 @@ class ReplayBuffer(Dataset):
         else:
             out, arr, ncols, idx_out = self._batch(B, record_idxs)
             if ix is None:
-                if len(self._out_cache) >= 2:
-                    self._out_cache.clear()
-                self._out_cache[id(out)] = (out, (B, record_idxs), (arr, ncols, idx_out))
+                self._out_remember(out, (B, record_idxs), (arr, ncols, idx_out))
         seed, call = self._next_seed()
         st = self._L.ogbx_replay_sample(self._hdr.data_ptr(), self._parity, self.max_size, arr, ncols, B,
                                         _lib.ptr(ix), seed, call, _lib.ptr(idx_out), self._empty.data_ptr(),
@@ -2063,7 +2130,7 @@ class ReplayBuffer(Dataset):
         return self.sample(num_idxs, record_idxs=True)['_idxs']
 
 
-class GCReplayBuffer(Dataset):
+class GCReplayBuffer(_BufferHost, Dataset):
     """Hindsight goal sampling over an on-device episode ring: what batched
     envs produce, one row per env and step, sampled as the reference's
     ``GCDataset.sample`` (datasets.py:213-327) samples a dataset
@@ -2144,8 +2211,8 @@ class GCReplayBuffer(Dataset):
         assert np.isclose(config['value_p_curgoal'] + config['value_p_trajgoal'] + config['value_p_randomgoal'], 1.0)
         assert np.isclose(config['actor_p_curgoal'] + config['actor_p_trajgoal'] + config['actor_p_randomgoal'], 1.0)
         self._cfg = _gc_config(config)
-        self._L = _bind()
-        self._dtype_code = _replay_dtypes()
+        self._init_host(seed)
+        self._sample_entry = self._L.ogbx_online_gc_sample
         self.ep_seq = torch.zeros(self.horizon, self.num_envs, dtype=torch.int32, device=self.device)
         self.cur_seq = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
         self.ep_end = torch.zeros(self.horizon, self.num_envs, dtype=torch.int64, device=self.device)
@@ -2153,18 +2220,6 @@ class GCReplayBuffer(Dataset):
                                 self.ep_end.data_ptr())
         self._done = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)  # add_step's terminated | truncated
         self._steps = 0
-        self._seed = int(seed) if seed is not None else None
-        self._calls = 0
-        self._ins_cache = {}
-        self._out_cache = {}
-        self._out_gen = self._gen
-        self._dev_idx = self.device.index
-        self._raw_stream = torch._C._cuda_getCurrentRawStream  # hipStream_t of the current stream, as an int
-
-    _next_seed = GCDataset._next_seed
-    _source = ReplayBuffer._source
-    _mask = ReplayBuffer._mask
-    _check_keys = ReplayBuffer._check_keys
 
     # ------------------------------------------------------------------- state
     @property
@@ -2196,27 +2251,9 @@ class GCReplayBuffer(Dataset):
     def _insert(self, specs, done, alt_select):
         """specs: (key, src, alt or None, op) per column, staged by
         ``_source``.  One launch; then S + 1."""
-        key = (done.data_ptr(), alt_select.data_ptr() if alt_select is not None else 0, self._gen) + tuple(
-            (k, s.data_ptr(), s.dtype, a.data_ptr() if a is not None else 0, op) for k, s, a, op in specs)
-        arr = self._ins_cache.get(key)
-        if arr is None:
-            code = self._dtype_code
-            cols = []
-            for k, s, a, op in specs:
-                col = self[k]
-                if len(col) != self.rows or not col.is_contiguous() or col.device != self.device:
-                    raise ValueError(f'buffer column {k!r} was replaced by one of another length, layout or device')
-                if col.dtype not in code or col.dtype is _torch().bool:
-                    raise ValueError(f'{k!r}: unsupported column dtype {col.dtype}')
-                if a is not None and a.dtype != s.dtype:
-                    raise ValueError(f'{k!r}: the alternative source has dtype {a.dtype}, the source {s.dtype}')
-                row = col[0].numel() if col.dim() > 1 else 1
-                cols.append(ReplayInsertColumn(col.data_ptr(), s.data_ptr(), a.data_ptr() if a is not None else None,
-                                               row, code[s.dtype], code[col.dtype], op, 0))
-            arr = (ReplayInsertColumn * len(cols))(*cols)
-            if len(self._ins_cache) >= 8:
-                self._ins_cache.clear()
-            self._ins_cache[key] = arr
+        # (the constructor bounds the column count)
+        arr = self._insert_columns(
+            specs, self.rows, (done.data_ptr(), alt_select.data_ptr() if alt_select is not None else 0))
         st = self._L.ogbx_online_insert(self._ring, arr, len(arr), done.data_ptr(),
                                         alt_select.data_ptr() if alt_select is not None else None,
                                         self._raw_stream(self._dev_idx))
@@ -2264,20 +2301,14 @@ class GCReplayBuffer(Dataset):
         torch = _torch()
         out, cols = {}, []
 
-        def add(src_key, dst_key, select):
-            src = self[src_key]
-            if len(src) != self.rows or not src.is_contiguous() or src.device != self.device:
-                raise ValueError(f'buffer column {src_key!r} was replaced by one of another length, layout or device')
-            dst = torch.empty((B,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
-            out[dst_key] = dst
-            row_bytes = (src[0].numel() if src.dim() > 1 else 1) * src.element_size()
-            cols.append(GcColumn(src.data_ptr(), dst.data_ptr(), row_bytes, select, 0))
-
-        for k in self.keys():
-            add(k, k, 0)
+        gather, rows = self._gather_column, self.rows
         goal_src = 'oracle_reps' if 'oracle_reps' in self else 'observations'  # datasets.py:348-357
-        add(goal_src, 'value_goals', 2)
-        add(goal_src, 'actor_goals', 3)
+        for k in self.keys():
+            out[k], col = gather(k, B, 0, rows)
+            cols.append(col)
+        for dst_key, select in (('value_goals', 2), ('actor_goals', 3)):
+            out[dst_key], col = gather(goal_src, B, select, rows)
+            cols.append(col)
         if len(cols) > REPLAY_MAX_COLS:
             raise ValueError(f'at most {REPLAY_MAX_COLS} columns per sample, got {len(cols)}')
         out['masks'] = torch.empty(B, dtype=torch.float64, device=self.device)
@@ -2303,11 +2334,17 @@ class GCReplayBuffer(Dataset):
         out: a batch returned by an earlier plain call with the same
         batch_size: refilled in place, stream ordered, and returned (a batch
         of another size raises ValueError).
+
+        ``HGCReplayBuffer.sample`` is this method over its own hooks:
+        HGCDataset.sample (datasets.py:496-643) over the snapshot, one launch.
+        With ``low_discount`` it also takes and records the ``l_*`` draws, and
+        a recording call returns the flat ``_idxs`` /
+        ``_high_value_goal_idxs`` / ``_high_actor_goal_idxs`` /
+        ``_low_value_goal_idxs``.
         """
-        torch = _torch()
         B = int(batch_size)
         if self._steps == 0:
-            raise ValueError('cannot sample from an empty GCReplayBuffer')
+            raise ValueError(f'cannot sample from an empty {self._NAME}')
         plain = idxs is None and not draws and not record_draws
         if self._out_gen != self._gen:  # a column was replaced
             self._out_cache.clear()
@@ -2316,51 +2353,79 @@ class GCReplayBuffer(Dataset):
         if hit is not None and hit[0] is out and hit[1] == B:
             call = self._calls
             self._calls = call + 1
-            st = self._L.ogbx_online_gc_sample(self._ring, self._cfg, hit[2][0], None, None, self._seed, call,
-                                               self._raw_stream(self._dev_idx))
+            st = self._sample_entry(*hit[2][0], self._seed, call, self._raw_stream(self._dev_idx))
             if st:
-                _lib.check(st, 'online_gc_sample')
+                _lib.check(st, self._what)
             return out
         if out is not None and len(out['masks']) != B:
             raise ValueError(f"out= holds a batch of {len(out['masks'])} samples, not {B}")
         out, held, idx_t = self._batch(B, record_draws)
+        dr, staged, rec, rec_t = self._stage(B, idxs, draws, record_draws)
+        seed, call = self._next_seed()
+        args = self._sample_args(held, dr, rec)
+        st = self._sample_entry(*args, seed, call, self._raw_stream(self._dev_idx))
+        _lib.check(st, self._what)
+        del staged  # alive until the launch was issued
+        if plain:
+            # a refill's leading arguments (a plain call has neither draws nor
+            # a record), and what keeps the descriptors alive
+            self._out_remember(out, B, (args, held))
+        if record_draws:
+            out['_draws'] = rec_t
+            out.update(idx_t)
+        return out
+
+    # ------------------------------------- what HGCReplayBuffer supplies instead
+    # (with _batch; the hook names of GCDataset / HGCDataset where they match)
+    _NAME = 'GCReplayBuffer'  # names the class in sample()'s message
+    _what = 'online_gc_sample'  # names the call in error messages
+    _draw_keys = _DRAW_ORDER  # the draws a call takes and a recording call reports
+
+    def _draw_structs(self):
+        """(injected draws to fill, its GC part)."""
+        dr = GcDraws()
+        return dr, dr
+
+    def _record_struct(self, rec_t):
+        return GcDrawRecord(*[rec_t[k].data_ptr() for k in _DRAW_ORDER])
+
+    def _sample_args(self, held, dr, rec):
+        """The arguments of ``_sample_entry`` before (seed, call, stream), from
+        what ``_batch`` returned second."""
+        return self._ring, self._cfg, held[0], dr, rec
+
+    def _stage(self, B, idxs, draws, record_draws):
+        """``GCDataset._stage`` for the ring: explicit idxs and injected draws
+        on the device and the record buffers of a recording call -- (draws
+        struct or None, tensors to keep alive until the launch was issued,
+        record struct or None, its tensors or None).  A wrong length or a draw
+        the sampler does not take raises ValueError."""
+        torch = _torch()
         dr = rec = rec_t = None
         staged = []
         if idxs is not None or draws:
-            dr = GcDraws()
+            dr, gdr = self._draw_structs()
             if idxs is not None:
                 t = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
                 if t.numel() != B:
                     raise ValueError(f'idxs must have {B} entries, got {t.numel()}')
                 staged.append(t)
-                dr.idxs = t.data_ptr()
+                gdr.idxs = t.data_ptr()
             for k, v in (draws or {}).items():
                 if k == 'idxs':
                     continue
-                if k not in _DRAW_ORDER:
+                if k not in self._draw_keys:
                     raise ValueError(f'unknown draw {k!r}')
-                t = _to_device(v, self.device).to(torch.int64 if k in _DRAW_INT else torch.float64).reshape(-1)
+                t = _to_device(v, self.device).to(torch.int64 if k in _HDRAW_INT else torch.float64).reshape(-1)
                 if t.numel() != B:
                     raise ValueError(f'draw {k!r} must have {B} entries, got {t.numel()}')
                 staged.append(t)
-                setattr(dr, k, t.data_ptr())
+                setattr(dr if k in _HDRAW_LOW else gdr, k, t.data_ptr())
         if record_draws:
-            rec_t = {k: torch.empty(B, dtype=torch.int64 if k in _DRAW_INT else torch.float64, device=self.device)
-                     for k in _DRAW_ORDER}
-            rec = GcDrawRecord(*[rec_t[k].data_ptr() for k in _DRAW_ORDER])
-        seed, call = self._next_seed()
-        st = self._L.ogbx_online_gc_sample(self._ring, self._cfg, held[0], dr, rec, seed, call,
-                                           self._raw_stream(self._dev_idx))
-        _lib.check(st, 'online_gc_sample')
-        del staged  # alive until the launch was issued
-        if plain:
-            if len(self._out_cache) >= 2:
-                self._out_cache.clear()
-            self._out_cache[id(out)] = (out, B, held)
-        if record_draws:
-            out['_draws'] = rec_t
-            out.update(idx_t)
-        return out
+            rec_t = {k: torch.empty(B, dtype=torch.int64 if k in _HDRAW_INT else torch.float64, device=self.device)
+                     for k in self._draw_keys}
+            rec = self._record_struct(rec_t)
+        return dr, staged, rec, rec_t
 
     def get_subset(self, idxs):
         return self.sample(len(idxs), idxs=idxs)
@@ -2414,17 +2479,13 @@ class HGCReplayBuffer(GCReplayBuffer):
     snapshot.  Nothing is read back.
     """
 
-    _HGC_KEYS = ('high_value_reps', 'high_value_goals', 'high_value_actions', 'high_value_next_observations',
-                 'high_value_offsets', 'high_value_subgoal_steps', 'high_value_masks', 'high_value_rewards',
-                 'low_value_next_observations', 'low_value_subgoal_steps', 'low_value_masks', 'low_value_rewards',
-                 'low_value_goals', 'high_actor_goals', 'high_actor_actions', 'high_actor_next_observations',
-                 'high_actor_targets', 'low_actor_goals', 'low_actor_goal_observations',
-                 'low_actor_next_observations')
+    _HGC_KEYS = tuple(k for k, _, _ in _HGC_LAYOUT if k not in GCReplayBuffer.RESERVED)
     RESERVED = GCReplayBuffer.RESERVED + _HGC_KEYS
     MAX_SAMPLE_COLS = 32  # kGcMaxCols
 
     def __init__(self, data, num_envs, horizon, config, device=None, seed=None):
         super().__init__(data, num_envs, horizon, config, device=device, seed=seed)
+        self._sample_entry = self._L.ogbx_online_hgc_sample
         c = config
         high = c.get('high_subgoal_steps', c['subgoal_steps'])
         self.value_subgoal_steps = int(high if c.get('value_subgoal_steps') is None else c['value_subgoal_steps'])
@@ -2450,124 +2511,35 @@ class HGCReplayBuffer(GCReplayBuffer):
         torch = _torch()
         out, cols = {}, []
 
-        def col(src_key, select):
-            src = self[src_key]
-            if len(src) != self.rows or not src.is_contiguous() or src.device != self.device:
-                raise ValueError(f'buffer column {src_key!r} was replaced by one of another length, layout or device')
-            dst = torch.empty((B,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
-            row_bytes = (src[0].numel() if src.dim() > 1 else 1) * src.element_size()
-            cols.append(GcColumn(src.data_ptr(), dst.data_ptr(), row_bytes, select, 0))
-            return dst
-
-        def scalar(dtype):
-            return torch.empty(B, dtype=dtype, device=self.device)
-
+        gather, rows = self._gather_column, self.rows
         for k in self.keys():
-            out[k] = col(k, 0)
+            out[k], col = gather(k, B, 0, rows)
+            cols.append(col)
         goal_src = 'oracle_reps' if 'oracle_reps' in self else 'observations'  # datasets.py:348-357
-        i64, f64 = torch.int64, torch.float64
-        out['high_value_reps'] = out['observations']
-        out['high_value_goals'] = col(goal_src, 2)
-        out['high_value_actions'] = col(goal_src, 4)
-        out['high_value_next_observations'] = col('observations', 4)
-        for k, dt in (('high_value_offsets', i64), ('high_value_subgoal_steps', i64), ('high_value_masks', f64),
-                      ('high_value_rewards', f64)):
-            out[k] = scalar(dt)
-        out['low_value_next_observations'] = col('observations', 5)
-        for k, dt in (('low_value_subgoal_steps', i64), ('low_value_masks', f64), ('low_value_rewards', f64)):
-            out[k] = scalar(dt)
-        if self._has_low:
-            out['low_value_goals'] = col(goal_src, 6)
-        out['value_goals'] = out['high_value_goals']
-        out['masks'] = scalar(f64)
-        out['rewards'] = scalar(f64)
-        out['high_actor_goals'] = col(goal_src, 3)
-        out['high_actor_actions'] = col(goal_src, 7)
-        out['high_actor_next_observations'] = col('observations', 7)
-        out['high_actor_targets'] = out['high_actor_actions']
-        out['low_actor_goals'] = col(goal_src, 8)
-        out['low_actor_goal_observations'] = col('observations', 8)
-        out['low_actor_next_observations'] = col('observations', 9)
+        for key, src_key, select in _hgc_outputs(out, B, goal_src, self._has_low, self.device):
+            out[key], col = gather(src_key, B, select, rows)
+            cols.append(col)
         if len(cols) > self.MAX_SAMPLE_COLS:
             raise ValueError(f'at most {self.MAX_SAMPLE_COLS} columns per sample, got {len(cols)}')
-        idx_t = {k: torch.empty(B, dtype=i64, device=self.device) for k in (_HGC_SCALARS[:4] if record else ())}
+        idx_t = {k: torch.empty(B, dtype=torch.int64, device=self.device)
+                 for k in (_HGC_SCALARS[:4] if record else ())}
         outs = HgcOutputs(*[_lib.ptr(idx_t.get(k)) for k in _HGC_SCALARS[:4]],
                           *[out[k].data_ptr() for k in _HGC_SCALARS[4:]])
         arr = (GcColumn * len(cols))(*cols)
-        return out, (arr, len(cols), outs), {'_' + k: t for k, t in idx_t.items()}
+        return out, (arr, len(cols), B, outs), {'_' + k: t for k, t in idx_t.items()}
 
-    def sample(self, batch_size, idxs=None, draws=None, record_draws=False, out=None):
-        """HGCDataset.sample (datasets.py:496-643) over the snapshot, one
-        launch.  Raises ValueError while no step was inserted.
+    # sample() is GCReplayBuffer's; what differs for the hierarchical sampler:
+    _NAME = 'HGCReplayBuffer'
+    _what = 'online_hgc_sample'
 
-        idxs: explicit flat rows of the snapshot, clamped into ``[0, L * N)``.
-        draws: injected reference draws (``_DRAW_ORDER``, with ``low_discount``
-        also the ``l_*`` draws), picks as flat rows.
-        record_draws: also return the draws used (``out['_draws']``; the
-        ``l_*`` draws only with ``low_discount``) and the flat ``_idxs`` /
-        ``_high_value_goal_idxs`` / ``_high_actor_goal_idxs`` /
-        ``_low_value_goal_idxs``.
-        out: a batch returned by an earlier plain call with the same
-        batch_size: refilled in place, stream ordered, and returned (a batch
-        of another size raises ValueError).
-        """
-        torch = _torch()
-        B = int(batch_size)
-        if self._steps == 0:
-            raise ValueError('cannot sample from an empty HGCReplayBuffer')
-        plain = idxs is None and not draws and not record_draws
-        if self._out_gen != self._gen:  # a column was replaced
-            self._out_cache.clear()
-            self._out_gen = self._gen
-        hit = self._out_cache.get(id(out)) if (out is not None and plain) else None
-        if hit is not None and hit[0] is out and hit[1] == B:
-            call = self._calls
-            self._calls = call + 1
-            arr, ncols, outs = hit[2]
-            st = self._L.ogbx_online_hgc_sample(self._ring, self._cfg, self._hcfg, arr, ncols, B, None, outs, None,
-                                                 self._seed, call, self._raw_stream(self._dev_idx))
-            if st:
-                _lib.check(st, 'online_hgc_sample')
-            return out
-        if out is not None and len(out['masks']) != B:
-            raise ValueError(f"out= holds a batch of {len(out['masks'])} samples, not {B}")
-        out, held, idx_t = self._batch(B, record_draws)
-        dr = rec = rec_t = None
-        staged = []
-        if idxs is not None or draws:
-            dr = HgcDraws()
-            if idxs is not None:
-                t = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
-                if t.numel() != B:
-                    raise ValueError(f'idxs must have {B} entries, got {t.numel()}')
-                staged.append(t)
-                dr.gc.idxs = t.data_ptr()
-            for k, v in (draws or {}).items():
-                if k == 'idxs':
-                    continue
-                if k not in self._draw_keys:
-                    raise ValueError(f'unknown draw {k!r}')
-                t = _to_device(v, self.device).to(torch.int64 if k in _HDRAW_INT else torch.float64).reshape(-1)
-                if t.numel() != B:
-                    raise ValueError(f'draw {k!r} must have {B} entries, got {t.numel()}')
-                staged.append(t)
-                setattr(dr if k in _HDRAW_LOW else dr.gc, k, t.data_ptr())
-        if record_draws:
-            rec_t = {k: torch.empty(B, dtype=torch.int64 if k in _HDRAW_INT else torch.float64, device=self.device)
-                     for k in self._draw_keys}
-            rec = HgcDrawRecord(GcDrawRecord(*[rec_t[k].data_ptr() for k in _DRAW_ORDER]),
-                                *[_lib.ptr(rec_t.get(k)) for k in _HDRAW_LOW])
-        seed, call = self._next_seed()
-        arr, ncols, outs = held
-        st = self._L.ogbx_online_hgc_sample(self._ring, self._cfg, self._hcfg, arr, ncols, B, dr, outs, rec, seed,
-                                             call, self._raw_stream(self._dev_idx))
-        _lib.check(st, 'online_hgc_sample')
-        del staged  # alive until the launch was issued
-        if plain:
-            if len(self._out_cache) >= 2:
-                self._out_cache.clear()
-            self._out_cache[id(out)] = (out, B, held)
-        if record_draws:
-            out['_draws'] = rec_t
-            out.update(idx_t)
-        return out
+    def _draw_structs(self):
+        dr = HgcDraws()
+        return dr, dr.gc
+
+    def _record_struct(self, rec_t):
+        # the l_* draws exist (and are recorded) only with low_discount
+        return HgcDrawRecord(super()._record_struct(rec_t), *[_lib.ptr(rec_t.get(k)) for k in _HDRAW_LOW])
+
+    def _sample_args(self, held, dr, rec):
+        arr, ncols, B, outs = held
+        return self._ring, self._cfg, self._hcfg, arr, ncols, B, dr, outs, rec
