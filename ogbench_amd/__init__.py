@@ -11,7 +11,10 @@ Drop-in for the hot path of hliuson/ogbench:
     ``datasets.ReplayBuffer``, batched on-device inserts and uniform sampling, and
     ``datasets.GCReplayBuffer``, hindsight goal sampling over an on-device episode
     ring filled by the batched envs, and ``datasets.HGCReplayBuffer``, the
-    hierarchical (HIQL) batch over the same ring.
+    hierarchical (HIQL) batch over the same ring;
+  * ``FrameStack`` ~ FrameStackWrapper of impls/utils/env_utils.py, the stacked
+    observations of a batched env composed on the device (``env_utils`` holds
+    the matching ``make_env_and_datasets(name, frame_stack=k)``).
 All compute runs in libogbx.so (HIP, gfx950); there is no CPU fallback.
 """
 
@@ -20,6 +23,7 @@ from .locomaze import MazeEnv, parse_env_id
 from .powderworld import PowderworldEnv
 from .registry import make, registered_env_ids
 from .utils import load_dataset, make_env_and_datasets
+from .wrappers import FrameStack
 
-__all__ = ['ATCDataset', 'Dataset', 'GCDataset', 'GCReplayBuffer', 'HGCDataset', 'HGCReplayBuffer', 'MazeEnv', 'PowderworldEnv', 'ReplayBuffer', 'load_dataset', 'make', 'make_env_and_datasets', 'parse_env_id',
+__all__ = ['ATCDataset', 'Dataset', 'FrameStack', 'GCDataset', 'GCReplayBuffer', 'HGCDataset', 'HGCReplayBuffer', 'MazeEnv', 'PowderworldEnv', 'ReplayBuffer', 'load_dataset', 'make', 'make_env_and_datasets', 'parse_env_id',
            'registered_env_ids']
