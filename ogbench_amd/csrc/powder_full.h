@@ -94,7 +94,9 @@ __device__ __forceinline__ uint32_t pw_rgb(const uint32_t* lut, uint32_t id, flo
 }
 
 // Rand-field purposes (Philox counter word w): goal replay forward s, the
-// reset's forward, the forward of elapsed step el.
+// reset's forward, the forward of elapsed step el.  The purpose is OR-ed into
+// bits 24-25, so the counters of one env-episode are distinct only while
+// elapsed and the goal index stay below 2^24.
 constexpr uint32_t kRandGoal = 1u << 24, kRandStart = 2u << 24, kRandStep = 3u << 24;
 
 __device__ __forceinline__ uint32_t fid(uint32_t a) { return a & 31u; }

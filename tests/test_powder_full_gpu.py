@@ -13,6 +13,7 @@ import torch
 import ogbench_amd
 from ogbench_amd import _lib
 from oracle import powder_full_np as orc
+from powder_worlds import seeded_world as _seeded_world
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), 'golden', 'powder_full_golden.npz')
@@ -55,21 +56,6 @@ def test_render_with_velocity(gpu, gold):
     assert np.array_equal(out.cpu().numpy(), gold['render_vel_world'])
     got = img.cpu().numpy()[0]
     assert np.array_equal(got, gold['render_vel_img']), _diff(got, gold['render_vel_img'])
-
-
-def _seeded_world(rng, n, size, ne):
-    """Random full worlds: elements of the set, walls on the border, random
-    velocities and momenta (the states a trajectory reaches)."""
-    elems = orc.ELEM_IDS[ne] + [0, 0, 0]
-    ids = rng.choice(elems, size=(n, size, size))
-    ids[:, 0, :] = ids[:, -1, :] = ids[:, :, 0] = ids[:, :, -1] = orc.WALL
-    w = orc.from_ids(ids)
-    w[:, 3:5] = (rng.randn(n, 2, size, size) * 2.5).astype(np.float32) * (rng.rand(n, 1, size, size) < 0.3)
-    w[:, 6] = rng.choice([-2, 0, 2], size=(n, size, size)) * np.isin(ids, orc.FLUIDS)
-    w[:, 8] = rng.rand(n, size, size) < 0.2
-    stone = ids == orc.STONE
-    w[:, 2] = np.where(stone, rng.rand(n, size, size) < 0.5, w[:, 2])
-    return w.astype(np.float32)
 
 
 @pytest.mark.parametrize('ne,size', [(5, 32), (8, 32), (8, 64)])
@@ -179,7 +165,8 @@ def test_philox_batch_consistency(gpu, ne, size):
     """Philox-driven batch: every env's step is the oracle forward of its
     previous state under SOME rand field -> check what is rand-independent:
     determinism per seed, state restore, success == goal-match < tol, obs ==
-    oracle render of the state, goals differ across envs (stochastic replay)."""
+    oracle render of the state, goals differ across envs (stochastic replay).
+    The fields themselves are replayed in tests/test_powder_philox_gpu.py."""
     n, K = 16, 24
     env = _env(gpu, n, ne=ne, size=size)
     tasks = torch.arange(n, device=gpu) % env.num_tasks + 1
