@@ -1,0 +1,245 @@
+// online_visual.hip -- image batches over the on-device episode ring on
+// gfx950: frame stacking and the random crop of GCDataset / HGCDataset over
+// the snapshot of an ogbx_online_ring in one launch
+// (include/ogbx_online_visual.h).
+//
+// Reference (hliuson/ogbench impls/utils/datasets.py):
+//   random_crop / batched_random_crop        17-33
+//   GCDataset.augment                        329-339
+//   GCDataset.get_stacked_observations       359-366
+// over the snapshot of the ring (include/ogbx_online.h): the live rows
+// unrolled env-major, flat index u = e * L + k for env e at step S - L + k.
+//
+// online_visual_gather_kernel: visual_gather_kernel's work layout (visual.hip)
+// -- one workgroup per (sample, image column), all columns of a sample on one
+// XCD -- with the index loads replaced by the ring's.  The workgroup
+// recomputes the column's selector from the flat index outputs of the sample
+// kernel (split_flat, episode_seq / episode_end_flat of online_device.h,
+// high_next of gc_select.h: the arithmetic of online_gc_sample_kernel and
+// online_hgc_sample_kernel), which leaves it with an env e and a live offset
+// k.  The stack's first row comes from the row's own ep_seq and at most F - 1
+// candidates, loaded together: offsets below 0 are dead steps and are not
+// read, for their slots hold newer rows of the same env.  The F source frames
+// then sit at unrelated physical rows ((slot0 + k') % T) * N + e, one of them
+// possibly in a second array (a column's alt: next_observations on selector
+// 0), and visual_tile.h stages and composes them through compose_frames.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "../../include/ogbx_online_visual.h"
+#include "common.h"
+#include "gc_select.h"
+#include "online_device.h"
+#include "visual_tile.h"
+
+namespace ogbx {
+
+struct OnVisColumns {
+  ogbx_online_visual_column c[OGBX_VISUAL_MAX_COLS];
+};
+
+struct OnVisArgs {
+  OnlineView ring;
+  const int64_t *idxs, *vg, *ag, *lvg;
+  int64_t k_value, k_low, k_actor;  // HGC subgoal steps
+  int32_t frame_stack, padding;
+  int32_t draw;
+  int32_t num_cols;
+  const int64_t* crop_from;
+  int64_t* crop_out;
+  uint32_t k0, k1, call_lo, call_hi;
+  uint32_t lds_bytes;
+  int64_t total;
+};
+
+// The env and the live offset of the row a column's selector picks for sample
+// s (numbering of ogbx_online_hgc_sample; every flat index clamped into
+// [0, L * N)).  The five derived selectors stay in [idx, fin], the sample's
+// env, as in online_hgc_sample_kernel: e < N and k < L either way.
+__device__ inline void select_ring_row(const OnVisArgs& a, int sel, int64_t s, int64_t* e, int64_t* k) {
+  const OnlineView& ring = a.ring;
+  const int64_t np = ring.npick;
+  const int64_t* direct = sel == 2 ? a.vg : (sel == 3 ? a.ag : (sel == 6 ? a.lvg : a.idxs));
+  const int64_t u = clamp_row(direct[s], np);
+  split_flat(ring, u, e, k);
+  if (sel == 0 || sel == 2 || sel == 3 || sel == 6) return;
+  // u is the sample's row; its episode's end, then the subgoal arithmetic
+  const int64_t fin = episode_end_flat(ring, episode_seq(ring, *e, phys_row(ring, *e, *k)), u, *e, *k);
+  int64_t next, steps;
+  if (sel == 4 || sel == 5) {
+    high_next(u, fin, clamp_row(a.vg[s], np), sel == 4 ? a.k_value : a.k_low, &next, &steps);
+  } else if (sel == 8) {
+    steps = a.k_actor < fin - u ? a.k_actor : fin - u;
+  } else {  // 7 high actor next, 9 low actor next
+    high_next(u, fin, clamp_row(a.ag[s], np), sel == 7 ? a.k_actor : a.k_low, &next, &steps);
+  }
+  *k += steps;  // 0 <= steps <= fin - u, and fin <= e * L + L - 1
+}
+
+// The live offset of the first row of the stack of n frames that ends at
+// offset k of env e: the earliest of k - (n-1) .. k that is live (>= 0) and
+// has the row's ep_seq.  The ordinals load together (no load waits for a
+// compare); ep_seq does not decrease along an env's live steps, so the rows
+// of the episode are the run that ends at k.
+__device__ __forceinline__ int64_t stack_first(const OnlineView& ring, int64_t e, int64_t k, int n) {
+  if (n <= 1) return k;
+  int32_t seq[OGBX_VISUAL_MAX_STACK] = {};
+#pragma unroll
+  for (int i = 0; i < OGBX_VISUAL_MAX_STACK; ++i)
+    if (i < n && k - i >= 0) seq[i] = ring.ep_seq[phys_row(ring, e, k - i)];
+  int run = 0;  // rows before k that belong
+  bool open = true;
+#pragma unroll
+  for (int i = 1; i < OGBX_VISUAL_MAX_STACK; ++i) {
+    open = open && i < n && k - i >= 0 && seq[i] == seq[0];
+    run += open ? 1 : 0;
+  }
+  return k - run;
+}
+
+__global__ void __launch_bounds__(kVisThreads) online_visual_gather_kernel(OnVisArgs a, OnVisColumns cols) {
+  extern __shared__ uint4 onvis_lds4[];  // 16-byte aligned
+  uint8_t* lds = reinterpret_cast<uint8_t*>(onvis_lds4);
+  // all columns of a sample on one XCD: see visual_gather_kernel
+  const int64_t b = blockIdx.x;
+  const int64_t x = b & 7, i = b >> 3;
+  const int64_t grp = i / a.num_cols;
+  const int c = (int)(i - grp * a.num_cols);
+  const int64_t s = grp * 8 + x;
+  if (s >= a.total) return;
+  const ogbx_online_visual_column& col = cols.c[c];
+  const int t = threadIdx.x;
+  const OnlineView& ring = a.ring;
+
+  int64_t e, k;
+  select_ring_row(a, col.select, s, &e, &k);
+  const int F = col.stack ? a.frame_stack : 1;
+  const uint8_t* __restrict__ src = static_cast<const uint8_t*>(col.src);
+  const uint8_t* __restrict__ alt = static_cast<const uint8_t*>(col.alt);
+  const int n = alt ? F - 1 : F;  // frames from src; alt's is the newest block
+  const int64_t kfirst = stack_first(ring, e, k, n);
+
+  const int p = a.padding;
+  int cy = p, cx = p;  // identity
+  if (a.crop_from || a.draw) {
+    int64_t oy, ox;
+    crop_offsets(a.crop_from, s, p, a.k0, a.k1, a.call_lo, a.call_hi, &oy, &ox);
+    if (col.crop) {
+      cy = (int)oy;
+      cx = (int)ox;
+    }
+    if (a.crop_out && c == 0 && t == 0) {
+      a.crop_out[2 * s] = oy;
+      a.crop_out[2 * s + 1] = ox;
+    }
+  }
+
+  const int64_t fb = (int64_t)col.height * (col.width * col.px_bytes);  // source frame bytes
+  uint8_t* dst = static_cast<uint8_t*>(col.dst) + s * (fb * F);
+  compose_frames(lds, a.lds_bytes, col.height, col.width, col.px_bytes, F, cy, cx, p, dst,
+                 [&](int j) -> const uint8_t* {
+                   if (alt && j == F - 1) return alt + phys_row(ring, e, k) * fb;
+                   int64_t kj = k - (n - 1 - j);
+                   kj = kj < kfirst ? kfirst : kj;  // kfirst >= 0: a live row
+                   return src + phys_row(ring, e, kj) * fb;
+                 });
+}
+
+}  // namespace ogbx
+
+using namespace ogbx;
+
+extern "C" {
+
+int32_t ogbx_online_visual_api_version(void) { return OGBX_ONLINE_VISUAL_API_VERSION; }
+
+ogbx_status ogbx_online_visual_gather(const ogbx_online_ring* ring, const ogbx_hgc_config* hcfg,
+                                      const ogbx_online_visual_column* cols, int32_t num_cols, int64_t total,
+                                      const ogbx_visual_indices* indices, int32_t frame_stack, int32_t padding,
+                                      const int64_t* crop_from, int32_t draw_crop, uint64_t seed,
+                                      uint64_t call_index, int64_t* crop_out, void* stream) {
+  const std::string who = "ogbx_online_visual_gather: ";
+  if (ogbx_status st = check_ring(ring, who)) return st;
+  OGBX_CHECK(cols && indices, OGBX_EINVAL, who + "null argument");
+  OGBX_CHECK(ring->steps >= 1, OGBX_EINVAL, who + "the ring is empty (steps must be >= 1)");
+  OGBX_CHECK(indices->idxs, OGBX_EINVAL, who + "indices->idxs is required");
+  OGBX_CHECK(num_cols >= 1 && num_cols <= OGBX_VISUAL_MAX_COLS, OGBX_EINVAL, who + "1 to 16 columns");
+  OGBX_CHECK(total > 0, OGBX_EINVAL, who + "total must be > 0");
+  OGBX_CHECK(frame_stack >= 1 && frame_stack <= OGBX_VISUAL_MAX_STACK, OGBX_EINVAL,
+             who + "frame_stack must be in 1..8");
+  OGBX_CHECK(padding >= 0 && padding < (1 << 20), OGBX_EINVAL, who + "padding must be >= 0");
+  OGBX_CHECK(!crop_out || crop_from || draw_crop, OGBX_EINVAL, who + "crop_out without crop offsets");
+  if (hcfg)
+    OGBX_CHECK(hcfg->value_subgoal_steps >= 0 && hcfg->low_subgoal_steps >= 0 && hcfg->actor_subgoal_steps >= 0,
+               OGBX_EINVAL, who + "negative subgoal steps");
+  const int max_select = hcfg ? kHgcSel - 1 : 3;
+  OnVisColumns vc{};
+  uint32_t lds = 16;
+  for (int i = 0; i < num_cols; ++i) {
+    const ogbx_online_visual_column& c = cols[i];
+    OGBX_CHECK(c.src && c.dst, OGBX_EINVAL, who + "null column pointer");
+    OGBX_CHECK(c.height > 0 && c.width > 0 && c.px_bytes > 0, OGBX_EINVAL, who + "bad image shape");
+    // the ring stores its own next_observations: no next-row selector
+    OGBX_CHECK(c.select >= 0 && c.select <= max_select && c.select != 1, OGBX_EINVAL,
+               who + "selector out of range");
+    const int s = c.select;
+    const bool need_v = s == 2 || s == 4 || s == 5, need_a = s == 3 || s == 7 || s == 9, need_l = s == 6;
+    OGBX_CHECK((!need_v || indices->value_goal_idxs) && (!need_a || indices->actor_goal_idxs) &&
+                   (!need_l || indices->low_value_goal_idxs),
+               OGBX_EINVAL, who + "a column selects through a missing index output");
+    const int64_t F = c.stack ? frame_stack : 1;
+    const int64_t row_bytes = (int64_t)c.width * c.px_bytes, frame = row_bytes * c.height;
+    OGBX_CHECK(frame * F <= (1ll << 30), OGBX_EINVAL, who + "image too large");
+    lds = std::max<uint32_t>(lds, vis_lds_bytes(frame, F));
+    vc.c[i] = c;
+  }
+  for (int i = 0; i < num_cols; ++i) {  // at least one image row per staged frame
+    const uint32_t F = cols[i].stack ? (uint32_t)frame_stack : 1u;
+    OGBX_CHECK((int64_t)((lds / F) & ~15u) >= (int64_t)cols[i].width * cols[i].px_bytes, OGBX_EINVAL,
+               who + "image row too wide to stage");
+  }
+  const int64_t blocks = ((total + 7) / 8) * 8 * num_cols;
+  OGBX_CHECK(blocks <= 0x7fffffffll, OGBX_EINVAL, who + "too many (sample, column) pairs for one launch");
+
+  int dev = 0;
+  OGBX_HIP(hipGetDevice(&dev));
+  bool ok = on_device(ring->ep_seq, dev) && on_device(ring->cur_seq, dev) && on_device(ring->ep_end, dev) &&
+            on_device(indices->idxs, dev);
+  for (const int64_t* q : {indices->value_goal_idxs, indices->actor_goal_idxs, indices->low_value_goal_idxs,
+                           crop_from, (const int64_t*)crop_out})
+    ok = ok && (!q || on_device(q, dev));
+  for (int i = 0; i < num_cols; ++i)
+    ok = ok && on_device(cols[i].src, dev) && on_device(cols[i].dst, dev) &&
+         (!cols[i].alt || on_device(cols[i].alt, dev));
+  OGBX_CHECK(ok, OGBX_EINVAL, who + "every pointer must be device memory of the current device");
+
+  OnVisArgs a{};
+  a.ring = online_view(*ring);
+  a.idxs = indices->idxs;
+  a.vg = indices->value_goal_idxs;
+  a.ag = indices->actor_goal_idxs;
+  a.lvg = indices->low_value_goal_idxs;
+  if (hcfg) {
+    a.k_value = hcfg->value_subgoal_steps;
+    a.k_low = hcfg->low_subgoal_steps;
+    a.k_actor = hcfg->actor_subgoal_steps;
+  }
+  a.frame_stack = frame_stack;
+  a.padding = padding;
+  a.draw = draw_crop != 0 && !crop_from;
+  a.crop_from = crop_from;
+  a.crop_out = crop_out;
+  seed_key(seed, hcfg ? kTagHgcSample : kTagGcSample, &a.k0, &a.k1);
+  a.call_lo = (uint32_t)call_index;
+  a.call_hi = (uint32_t)(call_index >> 32);
+  a.lds_bytes = lds;
+  a.num_cols = num_cols;
+  a.total = total;
+  hipLaunchKernelGGL(online_visual_gather_kernel, dim3((uint32_t)blocks), dim3(kVisThreads), lds,
+                     (hipStream_t)stream, a, vc);
+  OGBX_LAUNCHED("online_visual_gather_kernel");
+  return OGBX_OK;
+}
+
+}  // extern "C"

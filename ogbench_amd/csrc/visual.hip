@@ -91,19 +91,7 @@ __global__ void __launch_bounds__(kVisThreads) visual_gather_kernel(VisArgs a, V
   int cy = p, cx = p;  // identity
   if (a.crop_from || a.draw) {
     int64_t oy, ox;
-    if (a.crop_from) {
-      oy = a.crop_from[2 * s];
-      ox = a.crop_from[2 * s + 1];
-      // an out-of-range window start moves into range (lax.dynamic_slice)
-      oy = oy < 0 ? 0 : (oy > 2 * p ? 2 * p : oy);
-      ox = ox < 0 ? 0 : (ox > 2 * p ? 2 * p : ox);
-    } else {
-      const uint64_t su = (uint64_t)s;
-      const u32x4 w = philox4x32_10(
-          {(uint32_t)su, a.call_lo, (uint32_t)OGBX_VISUAL_CROP_SLOT, (uint32_t)(su >> 32) ^ a.call_hi}, a.k0, a.k1);
-      oy = bounded_u32(w.x, (uint32_t)(2 * p + 1));
-      ox = bounded_u32(w.y, (uint32_t)(2 * p + 1));
-    }
+    crop_offsets(a.crop_from, s, p, a.k0, a.k1, a.call_lo, a.call_hi, &oy, &ox);
     if (col.crop) {
       cy = (int)oy;
       cx = (int)ox;

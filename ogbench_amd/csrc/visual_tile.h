@@ -1,13 +1,19 @@
-// visual_tile.h -- what the image kernels of visual.hip and atc.hip share: one
-// workgroup stages the F source frames of one selector row (or a band of their
-// rows when they exceed the LDS budget) in LDS with the widest aligned loads
-// and composes one output image -- pixels of F * px_bytes bytes, shifted by
-// the crop -- from LDS in 16-byte units aligned to the destination.  Internal
-// to libogbx.
+// visual_tile.h -- what the image kernels of visual.hip, atc.hip and
+// online_visual.hip share: one workgroup stages the F source frames of one
+// selector row (or a band of their rows when they exceed the LDS budget) in
+// LDS with the widest aligned loads and composes one output image -- pixels of
+// F * px_bytes bytes, shifted by the crop -- from LDS in 16-byte units aligned
+// to the destination.  compose_frames takes the address of each block's frame,
+// so the unrelated physical rows of the episode ring compose with the code of
+// the offline datasets' consecutive rows (compose_image).  Internal to
+// libogbx.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "../../include/ogbx_visual.h"
+#include "common.h"
 
 namespace ogbx {
 
@@ -61,26 +67,24 @@ __device__ __forceinline__ int64_t stack_start(const int64_t* __restrict__ traj_
   return start;
 }
 
-// The output image of selector row r, by the whole workgroup of kVisThreads
-// threads: channel block j (0..F-1) is the frame at row
-// max(r - (F-1-j), start) with start = stack_start(traj_end, r, F); the window
-// starts at (cy, cx) of the image padded by p edge pixels ((p, p) is the
-// identity).  lds: lds_bytes of 16-byte aligned LDS with at least one image
-// row per staged frame ((lds_bytes / F) & ~15 >= width * px_bytes); dst: the
-// dense [height, width, F * px_bytes] destination.
-__device__ __forceinline__ void compose_image(uint8_t* lds, uint32_t lds_bytes, const VisGeom& g, int64_t r,
-                                              int64_t start, int F, int cy, int cx, int p,
-                                              uint8_t* __restrict__ dst) {
+// One output image by the whole workgroup of kVisThreads threads, from F
+// source frames that may lie anywhere: frame_at(j) is the address of the
+// dense [H, W, px] frame of channel block j (0..F-1); the window starts at
+// (cy, cx) of the image padded by p edge pixels ((p, p) is the identity).
+// lds: lds_bytes of 16-byte aligned LDS with at least one image row per staged
+// frame ((lds_bytes / F) & ~15 >= W * px); dst: the dense [H, W, F * px]
+// destination.
+template <class FrameAt>
+__device__ __forceinline__ void compose_frames(uint8_t* lds, uint32_t lds_bytes, int H, int W, int px, int F, int cy,
+                                               int cx, int p, uint8_t* __restrict__ dst, FrameAt frame_at) {
   const int t = threadIdx.x;
-  const int H = g.height, W = g.width, px = g.px_bytes;
   const int rb = W * px;               // source row bytes
   const int64_t fb = (int64_t)H * rb;  // source frame bytes
   const int opx = F * px;              // output pixel bytes
   const int orb = W * opx;             // output row bytes
-  const uint8_t* __restrict__ src = static_cast<const uint8_t*>(g.src);
 
   if (F == 1 && cy == p && cx == p) {  // a row copy
-    copy_bytes(dst, src + r * fb, fb);
+    copy_bytes(dst, frame_at(0), fb);
     return;
   }
 
@@ -91,11 +95,7 @@ __device__ __forceinline__ void compose_image(uint8_t* lds, uint32_t lds_bytes, 
     const int sy_lo = clampi(y0 + cy - p, H - 1), sy_hi = clampi(y1 - 1 + cy - p, H - 1);
     const int len = (sy_hi - sy_lo + 1) * rb;  // <= band * rb <= fstride
     if (y0 > 0) __syncthreads();               // the previous band was composed
-    for (int j = 0; j < F; ++j) {
-      int64_t row = r - (F - 1 - j);
-      row = row < start ? start : row;
-      copy_bytes(lds + j * fstride, src + row * fb + (int64_t)sy_lo * rb, len);
-    }
+    for (int j = 0; j < F; ++j) copy_bytes(lds + j * fstride, frame_at(j) + (int64_t)sy_lo * rb, len);
     __syncthreads();
 
     // compose rows [y0, y1) in 16-byte units aligned to the destination; the
@@ -143,6 +143,42 @@ __device__ __forceinline__ void compose_image(uint8_t* lds, uint32_t lds_bytes, 
           if (q >= b0 && q < b1) D[o0 + q] = (uint8_t)(w[q >> 2] >> (8 * (q & 3)));
       }
     }
+  }
+}
+
+// The output image of selector row r of a dense [R, height, width, px_bytes]
+// source: channel block j (0..F-1) is the frame at row max(r - (F-1-j), start)
+// with start = stack_start(traj_end, r, F).
+__device__ __forceinline__ void compose_image(uint8_t* lds, uint32_t lds_bytes, const VisGeom& g, int64_t r,
+                                              int64_t start, int F, int cy, int cx, int p,
+                                              uint8_t* __restrict__ dst) {
+  const int64_t fb = (int64_t)g.height * (g.width * g.px_bytes);  // source frame bytes
+  const uint8_t* __restrict__ src = static_cast<const uint8_t*>(g.src);
+  compose_frames(lds, lds_bytes, g.height, g.width, g.px_bytes, F, cy, cx, p, dst, [=](int j) {
+    int64_t row = r - (F - 1 - j);
+    row = row < start ? start : row;
+    return src + row * fb;
+  });
+}
+
+// The crop offsets (cy, cx) of sample s, each in [0, 2 p]: the injected pair
+// moved into range (lax.dynamic_slice moves an out-of-range window start),
+// else Philox words x, y of the counter {sample_lo, call_lo,
+// OGBX_VISUAL_CROP_SLOT, sample_hi ^ call_hi} reduced by multiply-high
+// (include/ogbx_visual.h).
+__device__ __forceinline__ void crop_offsets(const int64_t* __restrict__ crop_from, int64_t s, int p, uint32_t k0,
+                                             uint32_t k1, uint32_t call_lo, uint32_t call_hi, int64_t* oy,
+                                             int64_t* ox) {
+  if (crop_from) {
+    const int64_t y = crop_from[2 * s], x = crop_from[2 * s + 1];
+    *oy = y < 0 ? 0 : (y > 2 * p ? 2 * p : y);
+    *ox = x < 0 ? 0 : (x > 2 * p ? 2 * p : x);
+  } else {
+    const uint64_t su = (uint64_t)s;
+    const u32x4 w = philox4x32_10(
+        {(uint32_t)su, call_lo, (uint32_t)OGBX_VISUAL_CROP_SLOT, (uint32_t)(su >> 32) ^ call_hi}, k0, k1);
+    *oy = bounded_u32(w.x, (uint32_t)(2 * p + 1));
+    *ox = bounded_u32(w.y, (uint32_t)(2 * p + 1));
   }
 }
 

@@ -23,7 +23,10 @@ Batched, device-side counterparts of impls/utils/datasets.py (hliuson/ogbench):
                episode ring filled one row per env and step
                (``online_insert_kernel``) and sampled as the reference samples
                the snapshot of its live rows (``online_gc_sample_kernel``,
-               include/ogbx_online.h).
+               include/ogbx_online.h); with ``frame_stack`` / ``p_aug`` one
+               further launch composes the stacked, cropped image keys from
+               the unstacked ring (``online_visual_gather_kernel``,
+               include/ogbx_online_visual.h), for ``HGCReplayBuffer`` too.
 
 Every sample is ONE launch of ``gc_sample_kernel`` (libogbx): index draw,
 trajectory-end lookup, hindsight goal relabel and the row gathers of every
@@ -46,7 +49,8 @@ import weakref
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _online_visual
+from ._online_visual import OnlineVisualColumn
 
 
 def _torch():
@@ -488,6 +492,27 @@ def _gc_config(c):
     )
 
 
+def _visual_config(config, data):
+    """(frame_stack or None, p_aug, p_aug live?, visual?) of a sampler over
+    ``data``, for GCDataset and its subclasses and for the ring buffers.
+
+    The p_aug rule of every sample() path: one np.random.rand() per call when
+    p_aug > 0 and not evaluation, else none.  The reference draws whenever
+    p_aug is not None (impls/utils/datasets.py:278); with p_aug <= 0 its test
+    can never pass and the draw would only advance numpy's global stream
+    (which the samplers' Philox draws do not follow), so it is skipped.
+    visual: some column is stacked or may be cropped (4-D observations)."""
+    fs = config.get('frame_stack')
+    frame_stack = int(fs) if fs is not None else None
+    if fs is not None:
+        assert 1 <= frame_stack <= 8 and data['observations'].dim() >= 2
+    p_aug = config.get('p_aug')
+    live = p_aug is not None and float(p_aug) > 0.0
+    visual = fs is not None or (live and any(
+        data[k].dim() == 4 for k in ('observations', 'next_observations') if k in data))
+    return frame_stack, p_aug, live, visual
+
+
 class GCDataset:
     """Goal-conditioned sampler (reference: datasets.py:149-366).
 
@@ -588,12 +613,11 @@ class GCDataset:
         self.preprocess_frame_stack = preprocess_frame_stack
         self.size = dataset.size
         self.device = dataset.device
-        fs = config.get('frame_stack')
-        self._frame_stack = int(fs) if fs is not None else None
-        if fs is not None:
+        if config.get('frame_stack') is not None:
             # only compact (observation-only) datasets (datasets.py:206-208)
             assert 'next_observations' not in dataset
-            assert 1 <= self._frame_stack <= 8 and dataset['observations'].dim() >= 2
+        self._frame_stack, self._p_aug, self._p_aug_live, visual = _visual_config(config, dataset)
+        self._visual = visual and not _plain
         self._trl = not _plain and config.get('agent_name') in TRL_AGENTS
         if self._trl:
             if not self._TRL_OK:
@@ -662,18 +686,7 @@ class GCDataset:
         # plan (ogbx_gc_plan_*): the prepared output batches and the look-ahead
         # state live in libogbx, so a steady call is one lookup and one launch
         self._lookahead = bool(config.get('lookahead', self._LOOKAHEAD_DEFAULT))
-        # The p_aug rule of every sample() path: one np.random.rand() per call
-        # when p_aug > 0 and not evaluation, else none.  The reference draws
-        # whenever p_aug is not None (impls/utils/datasets.py:278); with
-        # p_aug <= 0 its test can never pass and the draw would only advance
-        # numpy's global stream (which this sampler's Philox draws do not
-        # follow), so it is skipped here.
-        self._p_aug = config.get('p_aug')
-        self._p_aug_live = self._p_aug is not None and float(self._p_aug) > 0.0
-        # visual: some column is stacked or may be cropped (4-D observations)
-        self._visual = not _plain and (fs is not None or (self._p_aug_live and any(
-            dataset[k].dim() == 4 for k in ('observations', 'next_observations') if k in dataset)))
-        self._vis_cache = {}
+        self._vis_cache = {}  # (_p_aug_live, _visual: _visual_config, above)
         self._trl_cache = {}
         self._dev_idx = self.device.index
         self._plan_sample = L.ogbx_gc_plan_sample
@@ -2163,11 +2176,47 @@ class GCReplayBuffer(_BufferHost, Dataset):
     also keeps the episode tables at O(1) per row (``ep_seq``, ``cur_seq``,
     ``ep_end``); ``sample`` is ONE launch of ``online_gc_sample_kernel``.
     Nothing is read back.  The regular layout only: the buffer stores its own
-    ``next_observations``; no ``valids``, no ``frame_stack``.
+    ``next_observations``; no ``valids``.
+
+    Visual buffers.  The config's ``frame_stack`` and ``p_aug`` are read by
+    ``GCDataset``'s rules.  The ring and ``snapshot()`` always hold UNSTACKED
+    frames (a ring of stacked frames would take F times the memory and insert
+    traffic).  With ``frame_stack = F`` (1..8), ``observations`` and, without
+    ``oracle_reps``, ``value_goals`` / ``actor_goals`` hold F frames joined on
+    the last axis: channel block j of a selector row at step t of env e is the
+    ``observations`` frame at step max(t - (F-1-j), s0), s0 the earliest step
+    among t - (F-1) .. t that is live and of t's episode -- the reference's
+    ``get_stacked_observations`` (datasets.py:359-366) over the snapshot, where
+    an episode whose head was overwritten starts at its oldest live row.
+    ``next_observations`` is the stack shifted by one: blocks 1 .. F-1 of the
+    stacked ``observations`` followed by the buffer's own ``next_observations``
+    row, which on every ``add_step`` history
+    (``next_observations[t] == observations[t+1]`` inside an episode) is the
+    reference's ``get_observations(idxs + 1)`` over the compact unrolling of
+    the snapshot.  2-D observations stack to ``[B, F * D]``.  With
+    ``p_aug > 0``, a call whose coin comes up (one ``np.random.rand()`` per
+    call; none under ``evaluation=True`` or with ``p_aug`` None or <= 0) crops
+    every 4-D key of ``_CROP_KEYS`` after stacking, with padding 3 and one
+    ``(cy, cx)`` per sample, injected as ``draws['crop_from']`` (``[B, 2]``) or
+    drawn on the device under the sampler's key at the call's
+    ``(seed, call)`` (Philox slot ``OGBX_VISUAL_CROP_SLOT``; a recording call
+    that cropped reports them as ``_draws['crop_from']``).  Such a ``sample``
+    is TWO launches: the sample kernel over the non-image columns, then
+    ``online_visual_gather_kernel`` (``ogbx_online_visual_gather``,
+    include/ogbx_online_visual.h) over the image columns.  Indices, ``masks``,
+    ``rewards`` and every non-image key are those of the same buffer without
+    the two keys at the same seed and call, which still issues the one launch.
     """
 
     RESERVED = ('masks', 'rewards', 'value_goals', 'actor_goals', 'valids')
     STEP_KEYS = ('observations', 'actions', 'next_observations', 'terminals')
+    # GCDataset's rules for the image keys (_visual_spec reads the columns
+    # through ``dataset``: for a ring, the buffer itself)
+    _VISUAL_KEYS = GCDataset._VISUAL_KEYS
+    _CROP_KEYS = GCDataset._CROP_KEYS
+    _visual_spec = GCDataset._visual_spec
+    _visual_indices = GCDataset._visual_indices
+    dataset = property(lambda self: self)
 
     @classmethod
     def create(cls, transition, num_envs, horizon, config, device=None, seed=None):
@@ -2220,6 +2269,15 @@ class GCReplayBuffer(_BufferHost, Dataset):
                                 self.ep_end.data_ptr())
         self._done = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)  # add_step's terminated | truncated
         self._steps = 0
+        self._frame_stack, self._p_aug, self._p_aug_live, self._visual = _visual_config(config, self)
+        if self._frame_stack is not None or self._p_aug_live:
+            # bound here, on the instance, and not tested for inside sample():
+            # a buffer without the two keys keeps its sample() as it was, the
+            # steady refill's one lookup and one ctypes call (as GCDataset
+            # binds its TRL sample)
+            self.sample = self._sample_visual
+            self._Lv = _online_visual.bind()
+            self._vis_cache = {}
 
     # ------------------------------------------------------------------- state
     @property
@@ -2297,18 +2355,47 @@ class GCReplayBuffer(_BufferHost, Dataset):
         self._insert(specs, done, done if alt is not None else None)
 
     # ----------------------------------------------------------------- sampling
-    def _batch(self, B, record):
+    def _vcolumn(self, src_key, dst_key, select, spec, B):
+        """(destination, descriptor) of one image column (GCDataset._vcolumn
+        for the ring).  A stacked ``next_observations`` is the stack over
+        ``observations`` with the buffer's own row as its newest block."""
+        stack, crop = spec
+        alt = None
+        if dst_key == 'next_observations' and src_key == 'next_observations' and stack:
+            alt, src_key = self._column_of('next_observations', self.rows), 'observations'
+        src = self._column_of(src_key, self.rows)
+        if alt is not None and (alt.shape != src.shape or alt.dtype != src.dtype):
+            raise ValueError("frame_stack needs 'next_observations' of the shape and dtype of 'observations'")
+        shape = tuple(src.shape[1:])
+        F = self._frame_stack if stack else 1
+        dst = self._new((B,) + shape[:-1] + (shape[-1] * F,), dtype=src.dtype, device=self.device)
+        # an image is [H, W, C]; any other row is a 1-row image of its leading elements
+        H, W = (shape[0], shape[1]) if len(shape) == 3 else (1, int(np.prod(shape[:-1], dtype=np.int64)))
+        return dst, OnlineVisualColumn(src.data_ptr(), alt.data_ptr() if alt is not None else None, dst.data_ptr(),
+                                       H, W, shape[-1] * src.element_size(), select, int(stack), int(crop))
+
+    def _gather(self, src_key, dst_key, select, B, cols, vcols):
+        """The destination of one output column; its descriptor goes to
+        ``vcols`` when it is an image column of a visual buffer, else to
+        ``cols`` (the sample kernel's)."""
+        spec = self._visual_spec(src_key, dst_key) if vcols is not None else None
+        if spec is not None:
+            dst, vc = self._vcolumn(src_key, dst_key, select, spec, B)
+            vcols.append(vc)
+        else:
+            dst, col = self._gather_column(src_key, B, select, self.rows)
+            cols.append(col)
+        return dst
+
+    def _batch(self, B, record, vcols=None):
         torch = _torch()
         out, cols = {}, []
 
-        gather, rows = self._gather_column, self.rows
         goal_src = 'oracle_reps' if 'oracle_reps' in self else 'observations'  # datasets.py:348-357
         for k in self.keys():
-            out[k], col = gather(k, B, 0, rows)
-            cols.append(col)
+            out[k] = self._gather(k, k, 0, B, cols, vcols)
         for dst_key, select in (('value_goals', 2), ('actor_goals', 3)):
-            out[dst_key], col = gather(goal_src, B, select, rows)
-            cols.append(col)
+            out[dst_key] = self._gather(goal_src, dst_key, select, B, cols, vcols)
         if len(cols) > REPLAY_MAX_COLS:
             raise ValueError(f'at most {REPLAY_MAX_COLS} columns per sample, got {len(cols)}')
         out['masks'] = torch.empty(B, dtype=torch.float64, device=self.device)
@@ -2323,17 +2410,24 @@ class GCReplayBuffer(_BufferHost, Dataset):
                             out['masks'].data_ptr(), out['rewards'].data_ptr())
         return out, (batch, arr), idx_t
 
-    def sample(self, batch_size, idxs=None, draws=None, record_draws=False, out=None):
+    def sample(self, batch_size, idxs=None, draws=None, record_draws=False, out=None, evaluation=False):
         """GCDataset.sample (datasets.py:213-294) over the snapshot, one
         launch.  Raises ValueError while no step was inserted.
 
         idxs: explicit flat rows of the snapshot, clamped into ``[0, L * N)``.
-        draws: injected reference draws (``_DRAW_ORDER``), picks as flat rows.
-        record_draws: also return the draws used (``out['_draws']``) and the
-        flat ``_idxs`` / ``_value_goal_idxs`` / ``_actor_goal_idxs``.
+        draws: injected reference draws (``_DRAW_ORDER``), picks as flat rows;
+        with ``p_aug`` also ``'crop_from'``, the ``[batch_size, 2]`` offsets
+        (cy, cx) of augment()'s randint (datasets.py:333), used when the call
+        crops.
+        record_draws: also return the draws used (``out['_draws']``, with
+        ``'crop_from'`` on a call that cropped) and the flat ``_idxs`` /
+        ``_value_goal_idxs`` / ``_actor_goal_idxs``.
         out: a batch returned by an earlier plain call with the same
         batch_size: refilled in place, stream ordered, and returned (a batch
         of another size raises ValueError).
+        evaluation: no augmentation and no coin (datasets.py:278); read only
+        with ``frame_stack`` / ``p_aug`` (``_sample_visual``, which a buffer
+        with either key runs in place of this method).
 
         ``HGCReplayBuffer.sample`` is this method over its own hooks:
         HGCDataset.sample (datasets.py:496-643) over the snapshot, one launch.
@@ -2374,6 +2468,69 @@ class GCReplayBuffer(_BufferHost, Dataset):
             out['_draws'] = rec_t
             out.update(idx_t)
         return out
+
+    def _sample_visual(self, batch_size, idxs=None, draws=None, record_draws=False, out=None, evaluation=False):
+        """sample() of a buffer with ``frame_stack`` or a live ``p_aug``
+        (``GCDataset._sample_visual`` for the ring): the coin, the sample
+        launch over the non-image columns with its index outputs requested,
+        then one ogbx_online_visual_gather launch over the image columns.  An
+        ``out=`` refill issues the same two launches and draws the same coin."""
+        torch = _torch()
+        B = int(batch_size)
+        if self._steps == 0:
+            raise ValueError(f'cannot sample from an empty {self._NAME}')
+        # the coin stays on the host (datasets.py:278-279); the offsets are device draws
+        crop = bool(self._p_aug_live and not evaluation and np.random.rand() < self._p_aug)
+        draws = dict(draws or {})
+        crop_from = draws.pop('crop_from', None)
+        cf = None
+        if crop and crop_from is not None and self._visual:
+            cf = _to_device(crop_from, self.device).to(torch.int64)
+            if tuple(cf.shape) != (B, 2):
+                raise ValueError(f"draws['crop_from'] must have shape ({B}, 2), got {tuple(cf.shape)}")
+        plain = idxs is None and not draws and crop_from is None and not record_draws
+        if self._out_gen != self._gen:  # a column was replaced
+            self._vis_cache.clear()
+            self._out_gen = self._gen
+        hit = self._vis_cache.get(id(out)) if (out is not None and plain) else None
+        if hit is not None and hit[0] is out and hit[1] == B:
+            st = hit[2]
+        else:
+            if out is not None and len(out['masks']) != B:
+                raise ValueError(f"out= holds a batch of {len(out['masks'])} samples, not {B}")
+            vcols = [] if self._visual else None
+            out, held, idx_t = self._batch(B, True, vcols)
+            nv = len(vcols or ())
+            if nv > REPLAY_MAX_COLS:  # OGBX_VISUAL_MAX_COLS
+                raise ValueError(f'at most {REPLAY_MAX_COLS} image columns per sample, got {nv}')
+            varr = (OnlineVisualColumn * max(1, nv))(*(vcols or ()))
+            st = (held, varr, nv, self._visual_indices(idx_t), idx_t)
+            if plain:
+                if len(self._vis_cache) >= 2:
+                    self._vis_cache.clear()
+                self._vis_cache[id(out)] = (out, B, st)
+        held, varr, nv, vidx, idx_t = st
+        dr, staged, rec, rec_t = self._stage(B, idxs, draws, record_draws)
+        seed, call = self._next_seed()
+        stream = self._raw_stream(self._dev_idx)
+        _lib.check(self._sample_entry(*self._sample_args(held, dr, rec), seed, call, stream), self._what)
+        cf_out = None
+        if nv:
+            if crop and record_draws:
+                cf_out = torch.empty((B, 2), dtype=torch.int64, device=self.device)
+            _lib.check(self._Lv.ogbx_online_visual_gather(
+                self._ring, self._hcfg_ptr(), varr, nv, B, vidx, self._frame_stack or 1, CROP_PADDING, _lib.ptr(cf),
+                int(crop and cf is None), seed, call, _lib.ptr(cf_out), stream), 'online_visual_gather')
+        del staged, cf  # alive until the launches were issued
+        if record_draws:
+            if cf_out is not None:
+                rec_t['crop_from'] = cf_out
+            out['_draws'] = rec_t
+            out.update(idx_t)
+        return out
+
+    def _hcfg_ptr(self):
+        return None  # HGCReplayBuffer passes its ogbx_hgc_config
 
     # ------------------------------------- what HGCReplayBuffer supplies instead
     # (with _batch; the hook names of GCDataset / HGCDataset where they match)
@@ -2477,6 +2634,14 @@ class HGCReplayBuffer(GCReplayBuffer):
     from ``oracle_reps`` when the buffer has that column, else from
     ``observations``.  Every index it takes or reports is a flat index of the
     snapshot.  Nothing is read back.
+
+    As a visual buffer (``frame_stack`` / ``p_aug``, see ``GCReplayBuffer``)
+    it stacks ``observations``, ``next_observations`` and the goal / "action"
+    / next-observation keys of ``HGCDataset._VISUAL_KEYS`` (the goal-type ones
+    only without ``oracle_reps``) and crops the keys of
+    ``HGCDataset._CROP_KEYS``: ``high_value_reps`` -- then a tensor of its own
+    -- and ``low_value_goals`` stay uncropped.  ``sample`` is then two
+    launches, ``online_hgc_sample_kernel`` and ``online_visual_gather_kernel``.
     """
 
     _HGC_KEYS = tuple(k for k, _, _ in _HGC_LAYOUT if k not in GCReplayBuffer.RESERVED)
@@ -2505,20 +2670,22 @@ class HGCReplayBuffer(GCReplayBuffer):
         )
 
     # ----------------------------------------------------------------- sampling
-    def _batch(self, B, record):
+    def _batch(self, B, record, vcols=None):
         """Output tensors in the reference's key order (HGCDataset._hcolumns),
-        the column descriptors and the scalar outputs."""
+        the column descriptors (the image columns of a visual buffer go to
+        ``vcols``) and the scalar outputs."""
         torch = _torch()
         out, cols = {}, []
 
-        gather, rows = self._gather_column, self.rows
         for k in self.keys():
-            out[k], col = gather(k, B, 0, rows)
-            cols.append(col)
+            out[k] = self._gather(k, k, 0, B, cols, vcols)
+        if vcols is not None:
+            # a visual batch's observations may be cropped; high_value_reps never is
+            out['high_value_reps'] = self._gather('observations', 'high_value_reps', 0, B, cols, vcols)
         goal_src = 'oracle_reps' if 'oracle_reps' in self else 'observations'  # datasets.py:348-357
-        for key, src_key, select in _hgc_outputs(out, B, goal_src, self._has_low, self.device):
-            out[key], col = gather(src_key, B, select, rows)
-            cols.append(col)
+        for key, src_key, select in _hgc_outputs(out, B, goal_src, self._has_low, self.device,
+                                                 own_reps=vcols is not None):
+            out[key] = self._gather(src_key, key, select, B, cols, vcols)
         if len(cols) > self.MAX_SAMPLE_COLS:
             raise ValueError(f'at most {self.MAX_SAMPLE_COLS} columns per sample, got {len(cols)}')
         idx_t = {k: torch.empty(B, dtype=torch.int64, device=self.device)
@@ -2531,6 +2698,12 @@ class HGCReplayBuffer(GCReplayBuffer):
     # sample() is GCReplayBuffer's; what differs for the hierarchical sampler:
     _NAME = 'HGCReplayBuffer'
     _what = 'online_hgc_sample'
+    _VISUAL_KEYS = HGCDataset._VISUAL_KEYS
+    _CROP_KEYS = HGCDataset._CROP_KEYS
+    _visual_indices = HGCDataset._visual_indices
+
+    def _hcfg_ptr(self):
+        return ctypes.byref(self._hcfg)
 
     def _draw_structs(self):
         dr = HgcDraws()
