@@ -26,7 +26,10 @@ Batched, device-side counterparts of impls/utils/datasets.py (hliuson/ogbench):
                include/ogbx_online.h); with ``frame_stack`` / ``p_aug`` one
                further launch composes the stacked, cropped image keys from
                the unstacked ring (``online_visual_gather_kernel``,
-               include/ogbx_online_visual.h), for ``HGCReplayBuffer`` too.
+               include/ogbx_online_visual.h), for ``HGCReplayBuffer`` too;
+               with a TRL ``agent_name`` the reference's TRL batch over the
+               snapshot (``online_trl_sample_kernel``,
+               include/ogbx_online_trl.h).
 
 Every sample is ONE launch of ``gc_sample_kernel`` (libogbx): index draw,
 trajectory-end lookup, hindsight goal relabel and the row gathers of every
@@ -49,7 +52,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib, _online_visual
+from . import _lib, _online_trl, _online_visual
 from ._online_visual import OnlineVisualColumn
 
 
@@ -183,6 +186,10 @@ _TRL_SCALARS = ('idxs', 'value_goal_idxs', 'actor_goal_idxs', 'value_midpoint_id
 _TRL_IMAGE_KEYS = ('value_goal_observations', 'actor_goal_observations', 'value_midpoint_observations',
                    'value_midpoint_goals', 'value_cur_goals', 'value_next_goals')
 TRL_SELECT_MIDPOINT = 4  # OGBX_TRL_SELECT_MIDPOINT
+# any other setting lets a value goal fall on or before its sample, where the
+# reference fails by its assert or by randint(low >= high)
+_TRL_VALUE_GOALS = ('a TRL agent needs value_p_curgoal == 0 and value_p_randomgoal == 0 '
+                    '(the value goal must lie past the sample in its trajectory)')
 
 
 class TrlOutputs(ctypes.Structure):
@@ -622,11 +629,8 @@ class GCDataset:
         if self._trl:
             if not self._TRL_OK:
                 raise NotImplementedError(f'{type(self).__name__}.sample has no TRL branch (nor has the reference)')
-            # any other setting lets a value goal fall on or before its sample,
-            # where the reference fails by its assert or by randint(low >= high)
             if config['value_p_curgoal'] != 0 or config['value_p_randomgoal'] != 0:
-                raise ValueError('a TRL agent needs value_p_curgoal == 0 and value_p_randomgoal == 0 '
-                                 '(the value goal must lie past the sample in its trajectory)')
+                raise ValueError(_TRL_VALUE_GOALS)
             self._VISUAL_KEYS = self._CROP_KEYS = type(self)._VISUAL_KEYS + _TRL_IMAGE_KEYS
             # a TRL sampler's sample() is bound here, on the instance, and not
             # tested for inside sample(): a steady GC / HGC refill is bounded by
@@ -2206,6 +2210,46 @@ class GCReplayBuffer(_BufferHost, Dataset):
     include/ogbx_online_visual.h) over the image columns.  Indices, ``masks``,
     ``rewards`` and every non-image key are those of the same buffer without
     the two keys at the same seed and call, which still issues the one launch.
+
+    TRL buffers.  With ``config['agent_name']`` in ``TRL_AGENTS`` ``sample``
+    runs the reference's TRL branch (datasets.py:198-204, 254-276) over the
+    snapshot: ``idxs`` and the random goals come only from the rows that are
+    not the last of their trajectory -- every live row but the last row of
+    each closed episode and each env's newest row -- and the batch carries the
+    value-midpoint keys in the reference's order, with ``GCDataset``'s rule of
+    one tensor per distinct (source, selector): ``actor_goal_observations is
+    value_goal_observations``; without ``oracle_reps`` also
+    ``value_goal_observations is value_goals``, ``value_midpoint_goals is
+    value_midpoint_observations`` and ``value_cur_goals is observations``; with
+    it ``value_cur_goals is oracle_reps``.  ``value_next_goals`` and
+    ``next_actions`` gather at flat row min(u + 1, L * N - 1), the snapshot's
+    ``observations[idxs + 1]`` / ``actions[idxs + 1]`` -- not the buffer's own
+    ``next_observations`` column, which differs from it at an auto-reset.
+    ``value_offsets`` / ``value_midpoint_offsets`` are int64.  The buffer
+    needs an ``actions`` column and ``steps >= 2`` to sample.
+
+    That pick table changes with every insert and is never built.  The buffer
+    keeps ``P``, the exclusive prefix sum over envs of their pickable rows
+    (``L - 1`` minus the episodes the env closed before its newest row, from
+    two rows of ``ep_seq``), and rebuilds it inside ``sample`` -- one scan,
+    ``ogbx_online_trl_table`` -- when ``steps``, the count of ``clear()``
+    calls or the stream changed since the last build (``trl_table_builds``
+    counts the builds): a sample after an insert is the scan and one launch of
+    ``online_trl_sample_kernel``, further samples at that step the one launch;
+    ``add`` / ``add_step`` are untouched.  The kernel turns a pick into a row
+    by a search over ``P`` for the env and one over the env's live closed
+    episodes in ``ep_end`` (include/ogbx_online_trl.h).  ``draws`` takes
+    ``'midpoint'`` and its ``pick`` / ``a_pick`` index the pick table;
+    ``record_draws`` reports ``_value_midpoint_idxs``.  Calls with explicit
+    ``idxs`` or injected draws read back the count of samples whose value goal
+    is not past the sample and raise ValueError with it; the Philox path
+    reads nothing back, and ``trl_bad_samples()`` reads its device counter,
+    nonzero only when a call found every live row ending an episode.  The
+    config needs ``value_p_curgoal == 0`` and ``value_p_randomgoal == 0``
+    (ValueError, as ``GCDataset``); a TRL buffer with ``frame_stack`` or a
+    live ``p_aug`` and ``HGCReplayBuffer`` with a TRL agent name raise
+    NotImplementedError at construction.  A buffer without a TRL agent name
+    keeps its ``sample``, its single launch and its batches.
     """
 
     RESERVED = ('masks', 'rewards', 'value_goals', 'actor_goals', 'valids')
@@ -2269,8 +2313,12 @@ class GCReplayBuffer(_BufferHost, Dataset):
                                 self.ep_end.data_ptr())
         self._done = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)  # add_step's terminated | truncated
         self._steps = 0
+        self._clears = 0  # clear() calls: with ``steps``, what a table derived from the ring depends on
         self._frame_stack, self._p_aug, self._p_aug_live, self._visual = _visual_config(config, self)
-        if self._frame_stack is not None or self._p_aug_live:
+        self._trl = config.get('agent_name') in TRL_AGENTS
+        if self._trl:
+            self._init_trl()  # binds sample on the instance too, for the same reason as below
+        elif self._frame_stack is not None or self._p_aug_live:
             # bound here, on the instance, and not tested for inside sample():
             # a buffer without the two keys keeps its sample() as it was, the
             # steady refill's one lookup and one ctypes call (as GCDataset
@@ -2304,6 +2352,7 @@ class GCReplayBuffer(_BufferHost, Dataset):
         rows stay where they are."""
         _lib.check(self._L.ogbx_online_clear(self._ring, _lib.stream_of(self.device)), 'online_clear')
         self._steps = self._ring.steps = 0
+        self._clears += 1
 
     # ------------------------------------------------------------------ inserts
     def _insert(self, specs, done, alt_select):
@@ -2529,6 +2578,161 @@ class GCReplayBuffer(_BufferHost, Dataset):
             out.update(idx_t)
         return out
 
+    # --------------------------------------------------------------- TRL batches
+    _TRL_OK = True  # the reference's GCDataset.sample has the TRL branch; HGCDataset.sample has none
+    _TRL_KEYS = ('value_goal_observations', 'actor_goal_observations', 'value_offsets', 'value_midpoint_offsets',
+                 'value_midpoint_observations', 'value_midpoint_actions', 'next_actions', 'value_midpoint_goals',
+                 'value_cur_goals', 'value_next_goals')  # datasets.py:261-276
+
+    def _init_trl(self):
+        """What a buffer with a TRL agent name adds at construction: the
+        config checks, the prefix table ``P`` with its scan storage, the
+        counter of bad samples, and ``sample`` bound to ``_sample_trl``."""
+        torch = _torch()
+        if not self._TRL_OK:
+            raise NotImplementedError(f'{self._NAME}.sample has no TRL branch (nor has the reference\'s HGCDataset)')
+        if self.config['value_p_curgoal'] != 0 or self.config['value_p_randomgoal'] != 0:
+            raise ValueError(_TRL_VALUE_GOALS)
+        if self._frame_stack is not None or self._p_aug_live:
+            raise NotImplementedError('TRL batches over the ring are not implemented for visual buffers: the config '
+                                      'has frame_stack or a live p_aug (p_aug > 0)')
+        if 'actions' not in self:
+            raise ValueError("a TRL GCReplayBuffer needs an 'actions' column")
+        bad = [k for k in self if k in self._TRL_KEYS]
+        if bad:
+            raise ValueError(f'a TRL GCReplayBuffer cannot have columns named {bad}: sample() returns keys of these '
+                             f'names')
+        L = self._Lt = _online_trl.bind()
+        need = ctypes.c_size_t(0)
+        _lib.check(L.ogbx_online_trl_table_bytes(self.num_envs, ctypes.byref(need)), 'online_trl_table_bytes')
+        self._trl_P = torch.zeros(self.num_envs + 1, dtype=torch.int64, device=self.device)
+        self._trl_tmp = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        self._trl_bad = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._trl_built = None  # (steps, clears, stream) P was built for
+        self.trl_table_builds = 0  # launches of the table scan so far
+        self.sample = self._sample_trl
+
+    def trl_bad_samples(self):
+        """Samples of Philox calls so far that had no row between the sample
+        and its value goal (one read of the device counter).  Nonzero only
+        when every live row ended an episode at the time of a call."""
+        return int(self._trl_bad.item())
+
+    def _trl_batch(self, B, record, checked):
+        """A new TRL batch (``GCDataset._trl_batch`` for the ring): the output
+        dict in the reference's key order (datasets.py:228-276), the
+        descriptors of its columns (selectors 0..4) and the scalar outputs.
+        Each distinct (source, selector) is gathered once; keys the reference
+        computes by the same expression share the tensor."""
+        torch = _torch()
+        out, cols, made = {}, [], {}
+
+        def add(src_key, dst_key, select):
+            dst = made.get((src_key, select))
+            if dst is None:
+                dst, col = self._gather_column(src_key, B, select, self.rows)
+                cols.append(col)
+                made[(src_key, select)] = dst
+            out[dst_key] = dst
+
+        def scalar(dtype):
+            return torch.empty(B, dtype=dtype, device=self.device)
+
+        i64, f64 = torch.int64, torch.float64
+        for k in self.keys():
+            add(k, k, 0)
+        goal_src = 'oracle_reps' if 'oracle_reps' in self else 'observations'  # datasets.py:348-357
+        add(goal_src, 'value_goals', 2)
+        add(goal_src, 'actor_goals', 3)
+        out['masks'], out['rewards'] = scalar(f64), scalar(f64)
+        add('observations', 'value_goal_observations', 2)
+        add('observations', 'actor_goal_observations', 2)  # the value goal, as the reference (datasets.py:262)
+        out['value_offsets'], out['value_midpoint_offsets'] = scalar(i64), scalar(i64)
+        add('observations', 'value_midpoint_observations', TRL_SELECT_MIDPOINT)
+        add('actions', 'value_midpoint_actions', TRL_SELECT_MIDPOINT)
+        add('actions', 'next_actions', 1)  # the snapshot's actions[idxs + 1]
+        add(goal_src, 'value_midpoint_goals', TRL_SELECT_MIDPOINT)
+        add(goal_src, 'value_cur_goals', 0)
+        add(goal_src, 'value_next_goals', 1)  # the snapshot's row idxs + 1, not the buffer's next_observations
+        idx_t = {'_' + k: scalar(i64) for k in (_TRL_SCALARS[:4] if record else ())}
+        # a checked call counts into a counter of its own and reads it back
+        bad = torch.zeros(1, dtype=i64, device=self.device) if checked else None
+        outs = TrlOutputs(*[_lib.ptr(idx_t.get('_' + k)) for k in _TRL_SCALARS[:4]],
+                          *[out[k].data_ptr() for k in _TRL_SCALARS[4:8]],
+                          (bad if checked else self._trl_bad).data_ptr())
+        arr = (GcColumn * len(cols))(*cols)  # at most 14 columns of the buffer and 8 further gathers
+        return out, (arr, len(cols), outs), idx_t, bad
+
+    def _sample_trl(self, batch_size, idxs=None, draws=None, record_draws=False, out=None, evaluation=False):
+        """sample() of a buffer whose config has a TRL agent name
+        (datasets.py:213-276 over the snapshot): the prefix table of the pick
+        counts is rebuilt when ``steps`` (or ``clear()``, or the stream)
+        changed since it was built -- one scan, ``ogbx_online_trl_table`` --
+        then ONE launch of ``online_trl_sample_kernel``
+        (``ogbx_online_trl_sample``, include/ogbx_online_trl.h).  Arguments as
+        ``sample``; ``draws`` also takes ``'midpoint'``, the rows of the
+        reference's ``randint(idxs, value_goal_idxs)``, and its ``pick`` /
+        ``a_pick`` index the pick table (every live row that is not the last
+        of its trajectory, in snapshot order).  Needs ``steps >= 2``."""
+        torch = _torch()
+        B = int(batch_size)
+        if self._steps < 2:
+            if self._steps == 0:
+                raise ValueError(f'cannot sample from an empty {self._NAME}')
+            raise ValueError(f'a TRL batch needs steps >= 2: the one live step of every env is the last row of its '
+                             f'trajectory, so no row can be picked')
+        draws = dict(draws or {})
+        midpoint = draws.pop('midpoint', None)
+        mid_in = None
+        if midpoint is not None:
+            mid_in = _to_device(midpoint, self.device).to(torch.int64).reshape(-1)
+            if mid_in.numel() != B:
+                raise ValueError(f"draws['midpoint'] must have {B} entries, got {mid_in.numel()}")
+        # explicit idxs or injected draws may put a value goal at or before its
+        # sample: such a call has the kernel count those samples and reads the
+        # count back (one sync); Philox draws on the pick table cannot
+        checked = idxs is not None or bool(draws) or mid_in is not None
+        plain = not checked and not record_draws
+        if self._out_gen != self._gen:  # a column was replaced
+            self._out_cache.clear()
+            self._out_gen = self._gen
+        hit = self._out_cache.get(id(out)) if (out is not None and plain) else None
+        idx_t, bad = {}, None
+        if hit is not None and hit[0] is out and hit[1] == B:
+            held = hit[2]
+        else:
+            if out is not None and len(out['masks']) != B:
+                raise ValueError(f"out= holds a batch of {len(out['masks'])} samples, not {B}")
+            out, held, idx_t, bad = self._trl_batch(B, record_draws, checked)
+            if plain:
+                self._out_remember(out, B, held)
+        arr, ncols, outs = held
+        dr, staged, rec, rec_t = self._stage(B, idxs, draws, record_draws)
+        mid_rec = torch.empty(B, dtype=torch.int64, device=self.device) if record_draws else None
+        seed, call = self._next_seed()
+        stream = self._raw_stream(self._dev_idx)
+        L = self._Lt
+        built = (self._steps, self._clears, stream)
+        if built != self._trl_built:
+            _lib.check(L.ogbx_online_trl_table(self._ring, self._trl_P.data_ptr(), self._trl_tmp.data_ptr(),
+                                               self._trl_tmp.numel(), stream), 'online_trl_table')
+            self._trl_built = built
+            self.trl_table_builds += 1
+        _lib.check(L.ogbx_online_trl_sample(self._ring, self._trl_P.data_ptr(), self._cfg, arr, ncols, B, dr,
+                                            _lib.ptr(mid_in), seed, call, outs, rec, _lib.ptr(mid_rec), stream),
+                   'online_trl_sample')
+        del staged, mid_in  # alive until the launch was issued
+        if bad is not None:
+            n = int(bad.item())
+            if n:
+                raise ValueError(f'online_trl_sample: {n} of {B} samples have no row between the sample and its '
+                                 f'value goal (an index names the last row of its trajectory, or the injected draws '
+                                 f'put the value goal at or before the sample)')
+        if record_draws:
+            rec_t['midpoint'] = mid_rec
+            out.update({'_draws': rec_t, **idx_t})
+        return out
+
     def _hcfg_ptr(self):
         return None  # HGCReplayBuffer passes its ogbx_hgc_config
 
@@ -2698,6 +2902,7 @@ class HGCReplayBuffer(GCReplayBuffer):
     # sample() is GCReplayBuffer's; what differs for the hierarchical sampler:
     _NAME = 'HGCReplayBuffer'
     _what = 'online_hgc_sample'
+    _TRL_OK = False  # as HGCDataset
     _VISUAL_KEYS = HGCDataset._VISUAL_KEYS
     _CROP_KEYS = HGCDataset._CROP_KEYS
     _visual_indices = HGCDataset._visual_indices
