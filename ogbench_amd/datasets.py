@@ -196,6 +196,30 @@ class TrlOutputs(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in _TRL_SCALARS]
 
 
+# What a TRL batch holds after the data's own keys, in the reference's order
+# (datasets.py:228-276), in the style of ``_HGC_LAYOUT``: (key, source, select)
+# is a gathered column, its source 'goal' being ``oracle_reps`` where the data
+# has it and ``observations`` otherwise; (key, 'scalar', dtype) a per-sample
+# output of the kernel.  Keys with one (source, select) share one tensor
+# (``_SamplerHost._trl_walk``).
+_TRL_LAYOUT = (
+    ('value_goals', 'goal', 2),
+    ('actor_goals', 'goal', 3),
+    ('masks', 'scalar', 'float64'),
+    ('rewards', 'scalar', 'float64'),
+    ('value_goal_observations', 'observations', 2),
+    ('actor_goal_observations', 'observations', 2),  # the value goal, as the reference (datasets.py:262)
+    ('value_offsets', 'scalar', 'int64'),
+    ('value_midpoint_offsets', 'scalar', 'int64'),
+    ('value_midpoint_observations', 'observations', TRL_SELECT_MIDPOINT),
+    ('value_midpoint_actions', 'actions', TRL_SELECT_MIDPOINT),
+    ('next_actions', 'actions', 1),  # the data's actions[idxs + 1]
+    ('value_midpoint_goals', 'goal', TRL_SELECT_MIDPOINT),
+    ('value_cur_goals', 'goal', 0),
+    ('value_next_goals', 'goal', 1),  # the data's row idxs + 1, not a stored next_observations
+)
+
+
 ATC_CROP_PADDING = 4  # ATCDataset.augment's default augment_padding (datasets.py:440)
 
 
@@ -520,7 +544,231 @@ def _visual_config(config, data):
     return frame_stack, p_aug, live, visual
 
 
-class GCDataset:
+class _CallHost:
+    """What every sampler keeps per call: the ``(seed, call)`` counter of its
+    Philox stream and the ``out=`` caches."""
+
+    def _next_seed(self):
+        if self._seed is None:
+            self._seed = int(np.random.randint(0, 2**63 - 1))
+        call = self._calls
+        self._calls += 1
+        return self._seed, call
+
+    # An out= cache: the last two batches that plain calls returned, by
+    # id(out), each with its shape and what a refill passes on.  A steady
+    # refill is host-bound (DESIGN 4.8, 4.11), so the lookup and the refill's
+    # one ctypes call stand in line in each sample(), not behind a call of
+    # their own; only a new batch comes through here.
+    @staticmethod
+    def _remember(cache, out, shape, *held):
+        if len(cache) >= 2:
+            cache.clear()
+        cache[id(out)] = (out, shape, *held)
+
+
+class _SamplerHost(_CallHost):
+    """The host side of goal-conditioned sampling that the dataset samplers
+    (``GCDataset``, ``HGCDataset``) and the ring buffers (``GCReplayBuffer``,
+    ``HGCReplayBuffer``) share: staging of explicit idxs and injected draws,
+    the draw hooks, the crop coin and the midpoint draw, the walks that lay a
+    GC and a TRL batch out, the image geometry of a visual column, the
+    bad-sample readback and the ``_*`` keys of a recording call.
+
+    A family supplies ``dataset`` (the columns, by key), ``device``, what
+    ``_visual_config`` returned (``_frame_stack``, ``_p_aug``, ``_p_aug_live``,
+    ``_visual``), ``_gather`` -- where a column comes from -- with
+    ``_VisualColumn``, its entry points (``_direct`` / ``_sample_entry``) and
+    its own ``out=`` caches and staleness test.  ``_HgcHost`` overrides the
+    hooks of the hierarchical samplers."""
+
+    # the keys a visual sampler may stack, and of those the ones augment() crops
+    _VISUAL_KEYS = ('observations', 'next_observations', 'value_goals', 'actor_goals')
+    _CROP_KEYS = _VISUAL_KEYS
+    _TRL_OK = True  # the reference's GCDataset.sample has the TRL branch; HGCDataset.sample has none
+    _draw_keys = _DRAW_ORDER  # the draws a call takes and a recording call reports
+    _strict_draws = True  # a draw the sampler does not take raises ValueError (GCDataset: is skipped)
+    _trl_bad = None  # where an unchecked TRL call counts its bad samples (the ring's device counter)
+
+    # ------------------------------------------------------------ draws, staging
+    def _draw_structs(self):
+        """(injected draws to fill, its GC part)."""
+        dr = GcDraws()
+        return dr, dr
+
+    def _record_struct(self, rec_t):
+        return GcDrawRecord(*[rec_t[k].data_ptr() for k in _DRAW_ORDER])
+
+    def _stage(self, total, idxs, draws, record_draws):
+        """Explicit idxs and injected draws on the device and the record
+        buffers of a recording call: (draws struct, or None when nothing is
+        injected; tensors to keep alive until the launch was issued; record
+        struct or None; its tensors or None).  A wrong length raises
+        ValueError, and so does a draw the sampler does not take
+        (``_strict_draws``)."""
+        torch = _torch()
+        dr = rec = rec_t = None
+        staged = []
+        if idxs is not None or draws:
+            dr, gdr = self._draw_structs()
+            if idxs is not None:
+                t = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
+                if t.numel() != total:
+                    raise ValueError(f'idxs must have {total} entries, got {t.numel()}')
+                staged.append(t)
+                gdr.idxs = t.data_ptr()
+            for k, v in (draws or {}).items():
+                if k == 'idxs':
+                    continue
+                if k not in self._draw_keys:
+                    if self._strict_draws:
+                        raise ValueError(f'unknown draw {k!r}')
+                    continue
+                t = _to_device(v, self.device).to(torch.int64 if k in _HDRAW_INT else torch.float64).reshape(-1)
+                if t.numel() != total:
+                    raise ValueError(f'draw {k!r} must have {total} entries, got {t.numel()}')
+                staged.append(t)
+                setattr(dr if k in _HDRAW_LOW else gdr, k, t.data_ptr())
+        if record_draws:
+            rec_t = {k: torch.empty(total, dtype=torch.int64 if k in _HDRAW_INT else torch.float64,
+                                    device=self.device) for k in self._draw_keys}
+            rec = self._record_struct(rec_t)
+        return dr, staged, rec, rec_t
+
+    # The crop coin (datasets.py:278-279: one np.random.rand() on the host; the
+    # offsets are device draws), the pops of 'crop_from' / 'midpoint' and the
+    # *checked* rule of a TRL call stand in line in each visual and TRL
+    # sample(): an out= refill passes them.  Only an injected draw comes here.
+    def _stage_crop_from(self, crop_from, total):
+        """Injected crop offsets as the [total, 2] int64 device tensor."""
+        cf = _to_device(crop_from, self.device).to(_torch().int64)
+        if tuple(cf.shape) != (total, 2):
+            raise ValueError(f"draws['crop_from'] must have shape ({total}, 2), got {tuple(cf.shape)}")
+        return cf
+
+    def _stage_midpoint(self, midpoint, total):
+        """Injected midpoint rows as an int64 device tensor of ``total``."""
+        mid_in = _to_device(midpoint, self.device).to(_torch().int64).reshape(-1)
+        if mid_in.numel() != total:
+            raise ValueError(f"draws['midpoint'] must have {total} entries, got {mid_in.numel()}")
+        return mid_in
+
+    @staticmethod
+    def _check_bad(bad, total, what):
+        """Read a checked TRL call's counter back and raise on bad samples."""
+        n = int(bad.item())
+        if n:
+            raise ValueError(f'{what}: {n} of {total} samples have no row between the sample and its value goal '
+                             f'(an index names the last row of its trajectory, or the injected draws put the value '
+                             f'goal at or before the sample)')
+
+    @staticmethod
+    def _recorded(rec_t, idx_t, **more):
+        """The ``_*`` keys a recording call adds to its batch: the draws used,
+        with those of ``more`` the call made, and the index outputs."""
+        rec_t.update((k, v) for k, v in more.items() if v is not None)
+        return {'_draws': rec_t, **idx_t}
+
+    # ----------------------------------------------------------- image columns
+    def _visual_spec(self, src_key, dst_key):
+        """(stack, crop) when ``dst_key`` is an image column of this visual
+        sampler (written by the visual gather), else None (a fused column)."""
+        if not self._visual or dst_key not in self._VISUAL_KEYS:
+            return None
+        if src_key not in ('observations', 'next_observations'):
+            return None  # oracle_reps: neither stacked nor cropped
+        stack = self._frame_stack is not None
+        crop = self._p_aug_live and self.dataset[src_key].dim() == 4 and dst_key in self._CROP_KEYS
+        return (stack, crop) if (stack or crop) else None
+
+    def _image_column(self, src, lead, select, spec, total):
+        """Destination tensor and descriptor (``_VisualColumn``, whose leading
+        source fields are ``lead``) of one image column over ``src``."""
+        stack, crop = spec
+        shape = tuple(src.shape[1:])
+        F = self._frame_stack if stack else 1
+        dst = _torch().empty((total,) + shape[:-1] + (shape[-1] * F,), dtype=src.dtype, device=self.device)
+        # an image is [H, W, C]; any other row is a 1-row image of its leading elements
+        H, W = (shape[0], shape[1]) if len(shape) == 3 else (1, int(np.prod(shape[:-1], dtype=np.int64)))
+        return dst, self._VisualColumn(*lead, dst.data_ptr(), H, W, shape[-1] * src.element_size(), select,
+                                       int(stack), int(crop))
+
+    def _hcfg_ptr(self):
+        return None  # the hierarchical samplers pass their ogbx_hgc_config
+
+    def _visual_indices(self, idx_t):
+        """The fused launch's index outputs as the visual gather reads them."""
+        return VisualIndices(idx_t['_idxs'].data_ptr(), idx_t['_value_goal_idxs'].data_ptr(),
+                             idx_t['_actor_goal_idxs'].data_ptr(), None)
+
+    # ------------------------------------------------------------ batch layouts
+    def _own_columns(self):
+        """(source key, batch key, selector) of the data's own keys."""
+        return [(k, k, 0) for k in self.dataset]
+
+    def _goal_source(self):
+        return 'oracle_reps' if 'oracle_reps' in self.dataset else 'observations'  # datasets.py:348-357
+
+    def _gc_walk(self, total, vcols=None):
+        """The gathered keys of a GC batch in the reference's order, and the
+        fused columns' descriptors (image columns go to ``vcols``)."""
+        out, cols = {}, []
+        for src_key, key, select in self._own_columns():
+            out[key] = self._gather(src_key, key, select, total, cols, vcols)
+        goal_src = self._goal_source()
+        for key, select in (('value_goals', 2), ('actor_goals', 3)):
+            out[key] = self._gather(goal_src, key, select, total, cols, vcols)
+        return out, cols
+
+    def _trl_walk(self, total, record, checked, vcols=None, mcols=None):
+        """A new TRL batch: the data's own keys, then ``_TRL_LAYOUT``.  Each
+        distinct (source, selector) is gathered once; keys the reference
+        computes by the same expression share the tensor.  Image columns go to
+        ``vcols``, those selected through the midpoint to ``mcols``.  Returns
+        the batch, the fused columns' descriptors, ``TrlOutputs``, the index
+        outputs -- there only when something reads them, the gathers of a
+        visual batch or a recording call -- and the bad-sample counter of a
+        checked call (else None: ``_trl_bad`` counts)."""
+        torch = _torch()
+        out, cols, made = {}, [], {}
+        goal_src = self._goal_source()
+
+        # ``made`` is keyed by (source, selector) alone: every observation-valued
+        # key of the layout is an image key of a visual TRL sampler, so whether
+        # a column is stacked or cropped depends on its source only
+        assert vcols is None or all(k in self._CROP_KEYS for k, what, _ in _TRL_LAYOUT
+                                    if what in ('observations', 'goal'))
+
+        def add(src_key, key, select):
+            dst = made.get((src_key, select))
+            if dst is None:
+                mid = mcols is not None and select == TRL_SELECT_MIDPOINT
+                n = len(mcols) if mid else 0
+                dst = made[(src_key, select)] = self._gather(src_key, key, select, total, cols,
+                                                             mcols if mid else vcols)
+                if mid and len(mcols) > n:
+                    # the midpoint's image columns go to a gather of their own,
+                    # which reads value_midpoint_idxs as its idxs (selector 0)
+                    mcols[-1].select = 0
+            out[key] = dst
+
+        for src_key, key, select in self._own_columns():
+            add(src_key, key, select)
+        for key, what, arg in _TRL_LAYOUT:
+            if what == 'scalar':
+                out[key] = torch.empty(total, dtype=getattr(torch, arg), device=self.device)
+            else:
+                add(goal_src if what == 'goal' else what, key, arg)
+        idx_t = {'_' + k: torch.empty(total, dtype=torch.int64, device=self.device)
+                 for k in (_TRL_SCALARS[:4] if (record or vcols is not None) else ())}
+        bad = torch.zeros(1, dtype=torch.int64, device=self.device) if checked else None
+        outs = TrlOutputs(*[_lib.ptr(idx_t.get('_' + k)) for k in _TRL_SCALARS[:4]],
+                          *[out[k].data_ptr() for k in _TRL_SCALARS[4:8]],
+                          _lib.ptr(bad if checked else self._trl_bad))
+        return out, cols, outs, idx_t, bad
+
+
+class GCDataset(_SamplerHost):
     """Goal-conditioned sampler (reference: datasets.py:149-366).
 
     config keys read (as the reference): discount, value_/actor_ p_curgoal,
@@ -606,10 +854,11 @@ class GCDataset:
     ``observations`` unless they come from ``oracle_reps``.
     """
 
-    # the keys a visual sampler may stack, and of those the ones augment() crops
-    _VISUAL_KEYS = ('observations', 'next_observations', 'value_goals', 'actor_goals')
-    _CROP_KEYS = _VISUAL_KEYS
-    _TRL_OK = True  # the reference's GCDataset.sample has the TRL branch; HGCDataset.sample has none
+    _VisualColumn = VisualColumn  # ogbx_visual_gather's descriptor
+    # the dataset samplers skip a draw they do not take: the fixtures recorded
+    # from the reference hand HGCDataset every draw the reference made, among
+    # them an 'l_dist' that no kernel reads (tests/golden/hgc_golden.npz)
+    _strict_draws = False
 
     def __init__(self, dataset, config, preprocess_frame_stack=True, seed=None, _plain=False):
         torch = _torch()
@@ -790,71 +1039,43 @@ class GCDataset:
             return GcColumn(self._record.data_ptr() + o, dst.data_ptr(), row_bytes, select, self._rec_stride)
         return GcColumn(src.data_ptr(), dst.data_ptr(), row_bytes, select, 0)
 
-    def _next_seed(self):
-        if self._seed is None:
-            self._seed = int(np.random.randint(0, 2**63 - 1))
-        call = self._calls
-        self._calls += 1
-        return self._seed, call
-
-    def _visual_spec(self, src_key, dst_key):
-        """(stack, crop) when ``dst_key`` is an image column of this visual
-        sampler (written by ogbx_visual_gather), else None (a fused column)."""
-        if not self._visual or dst_key not in self._VISUAL_KEYS:
-            return None
-        if src_key not in ('observations', 'next_observations'):
-            return None  # oracle_reps: neither stacked nor cropped
-        stack = self._frame_stack is not None
-        crop = self._p_aug_live and self.dataset[src_key].dim() == 4 and dst_key in self._CROP_KEYS
-        return (stack, crop) if (stack or crop) else None
-
-    def _vcolumn(self, src_key, select, spec, total):
-        """Destination tensor and descriptor of one image column."""
+    def _gather(self, src_key, dst_key, select, total, cols, vcols):
+        """The destination of one output column.  Its descriptor goes to
+        ``vcols`` when it is an image column of a visual sampler (``vcols``
+        None: no column is), else to ``cols``, the fused launch's, read from
+        the row record when the key lives there."""
         src = self.dataset[src_key]
-        stack, crop = spec
-        shape = tuple(src.shape[1:])
-        F = self._frame_stack if stack else 1
-        dst = _torch().empty((total,) + shape[:-1] + (shape[-1] * F,), dtype=src.dtype, device=self.device)
-        # an image is [H, W, C]; any other row is a 1-row image of its leading elements
-        H, W = (shape[0], shape[1]) if len(shape) == 3 else (1, int(np.prod(shape[:-1], dtype=np.int64)))
-        return dst, VisualColumn(src.data_ptr(), dst.data_ptr(), H, W, shape[-1] * src.element_size(), select,
-                                 int(stack), int(crop))
+        spec = self._visual_spec(src_key, dst_key) if vcols is not None else None
+        if spec is not None:
+            dst, vc = self._image_column(src, (src.data_ptr(),), select, spec, total)
+            vcols.append(vc)
+        else:
+            dst = _torch().empty((total,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
+            cols.append(self._column(src_key, dst, select))
+        return dst
+
+    def _own_columns(self):
+        own = super()._own_columns()
+        if 'next_observations' not in self.dataset:
+            own.append(('observations', 'next_observations', 1))  # datasets.py:81-82
+        return own
 
     def _columns(self, total, keys, vcols=None):
         """Column descriptors and the output dict (reference key order); the
-        image columns of a visual sampler go to ``vcols``."""
-        torch = _torch()
-        ds = self.dataset
+        image columns of a visual sampler go to ``vcols``.  ``keys``: those of
+        the dataset's keys to gather and nothing else (``get_random_idxs``)."""
+        if keys is None and not self._plain:
+            return self._gc_walk(total, vcols)
         out, cols = {}, []
-
-        def add(src_key, dst_key, select):
-            spec = self._visual_spec(src_key, dst_key) if vcols is not None else None
-            if spec is not None:
-                out[dst_key], vc = self._vcolumn(src_key, select, spec, total)
-                vcols.append(vc)
-                return
-            src = ds[src_key]
-            dst = torch.empty((total,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
-            out[dst_key] = dst
-            cols.append(self._column(src_key, dst, select))
-
-        for k in (ds.keys() if keys is None else keys):
-            add(k, k, 0)
-        if keys is None and 'next_observations' not in ds:
-            add('observations', 'next_observations', 1)  # datasets.py:81-82
-        if not self._plain and keys is None:
-            goal_src = 'oracle_reps' if 'oracle_reps' in ds else 'observations'  # datasets.py:348-357
-            add(goal_src, 'value_goals', 2)
-            add(goal_src, 'actor_goals', 3)
+        for src_key, key, select in (self._own_columns() if keys is None else [(k, k, 0) for k in keys]):
+            out[key] = self._gather(src_key, key, select, total, cols, vcols)
         return out, cols
+
 
     # GC: with the look-ahead actually hitting (round 5), 4.7 vs 5.8 us per
     # B = 1,024 launch back to back (profiles/r05_gcsample_*), so on by
     # default for both samplers
     _LOOKAHEAD_DEFAULT = True
-
-    def _hcfg_ptr(self):
-        return None  # GCDataset; HGCDataset passes its ogbx_hgc_config
 
     def _plan_for(self, seed):
         """The sampler plan of this (dataset, config, seed), created on the
@@ -888,8 +1109,8 @@ class GCDataset:
         return slot
 
     # ------------------------------------------ what HGCDataset supplies instead
+    # (with the hooks of _SamplerHost that _HgcHost overrides)
     _what = 'gc_sample'  # names the call in error messages
-    _draw_keys = _DRAW_ORDER  # the draws a recording call reports
 
     def _batch(self, total, keys, record, vcols=None):
         """A new batch: the output dict, the column descriptors, the scalar
@@ -910,14 +1131,6 @@ class GCDataset:
             out['rewards'] = rewards
         scalars = tuple(map(_lib.ptr, (idx, vg, ag, masks, rewards)))
         return out, cols, scalars, (masks, rewards), {'_idxs': idx, '_value_goal_idxs': vg, '_actor_goal_idxs': ag}
-
-    def _draw_structs(self):
-        """(injected draws to fill, its GC part)."""
-        dr = GcDraws()
-        return dr, dr
-
-    def _record_struct(self, rec_t):
-        return GcDrawRecord(*[rec_t[k].data_ptr() for k in _DRAW_ORDER])
 
     def _set_batch(self, plan, slot, col_arr, ncols, B, nb, scalars):
         return self._L.ogbx_gc_plan_set_batch(plan, slot, col_arr, ncols, B, nb, *scalars, None)
@@ -979,38 +1192,7 @@ class GCDataset:
             out.update(extra)
         return out
 
-    def _stage(self, total, idxs, draws, record_draws):
-        """Explicit idxs and injected draws on the device, and the record
-        buffers of a recording call: (draws struct, tensors to keep alive until
-        the launch was issued, record struct or None, its tensors or None)."""
-        torch = _torch()
-        staged = []
-        dr, gdr = self._draw_structs()
-        if idxs is not None:
-            t = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
-            assert t.numel() == total
-            staged.append(t)
-            gdr.idxs = t.data_ptr()
-        for k, v in (draws or {}).items():
-            if k == 'idxs':
-                continue
-            t = _to_device(v, self.device).to(torch.int64 if k in _HDRAW_INT else torch.float64).reshape(-1)
-            assert t.numel() == total, k
-            staged.append(t)
-            setattr(gdr if hasattr(gdr, k) else dr, k, t.data_ptr())
-        rec = rec_t = None
-        if record_draws:
-            rec_t = {k: torch.empty(total, dtype=torch.int64 if k in _HDRAW_INT else torch.float64,
-                                    device=self.device) for k in self._draw_keys}
-            rec = self._record_struct(rec_t)
-        return dr, staged, rec, rec_t
-
     # ------------------------------------------------------------ visual batches
-    def _visual_indices(self, idx_t):
-        """The fused launch's index outputs as ogbx_visual_gather reads them."""
-        return VisualIndices(idx_t['_idxs'].data_ptr(), idx_t['_value_goal_idxs'].data_ptr(),
-                             idx_t['_actor_goal_idxs'].data_ptr(), None)
-
     def _sample_visual(self, B, nb, idxs, evaluation, draws, record_draws, out):
         """sample() of a visual sampler: the fused direct launch over the
         non-image columns with the index outputs requested, then one
@@ -1022,15 +1204,10 @@ class GCDataset:
                 or (self._rec_src and tuple(map(_VERSION, self._rec_tensors)) != self._rec_versions)):
             self._refresh_record()
             self._vis_cache.clear()
-        # the coin stays on the host (datasets.py:278-279); the offsets are device draws
         crop = bool(self._p_aug_live and not evaluation and np.random.rand() < self._p_aug)
         draws = dict(draws or {})
         crop_from = draws.pop('crop_from', None)
-        cf = None
-        if crop and crop_from is not None:
-            cf = _to_device(crop_from, self.device).to(torch.int64)
-            if tuple(cf.shape) != (total, 2):
-                raise ValueError(f"draws['crop_from'] must have shape ({total}, 2), got {tuple(cf.shape)}")
+        cf = self._stage_crop_from(crop_from, total) if (crop and crop_from is not None) else None
         # as in the fused path, only a call without idxs / draws / recording
         # prepares a batch that ``out=`` can refill
         plain_call = idxs is None and not draws and crop_from is None and not record_draws
@@ -1045,9 +1222,7 @@ class GCDataset:
             st = (ctypes.cast(col_keep, ctypes.c_void_p), len(cols), scalars, ctypes.cast(vcol_keep, ctypes.c_void_p),
                   len(vcols), self._visual_indices(idx_t), idx_t, (col_keep, vcol_keep, keep))
             if plain_call:
-                if len(self._vis_cache) >= 2:
-                    self._vis_cache.clear()
-                self._vis_cache[id(out)] = (out, (B, nb), st)
+                self._remember(self._vis_cache, out, (B, nb), st)
         col_arr, ncols, scalars, vcol_arr, nvcols, vidx, idx_t, _ = st
         dr, staged, rec, rec_t = self._stage(total, idxs, draws, record_draws)
         cf_out = torch.empty((total, 2), dtype=torch.int64, device=self.device) if (crop and record_draws) else None
@@ -1059,9 +1234,7 @@ class GCDataset:
             _lib.ptr(cf), int(crop and cf is None), seed, call, _lib.ptr(cf_out), stream), 'visual_gather')
         del staged, cf  # alive until the launches were issued
         if record_draws:
-            if cf_out is not None:
-                rec_t['crop_from'] = cf_out
-            out.update({'_draws': rec_t, **idx_t})
+            out.update(self._recorded(rec_t, idx_t, crop_from=cf_out))
         return out
 
     # --------------------------------------------------------------- TRL batches
@@ -1082,60 +1255,15 @@ class GCDataset:
         those selected through the midpoint, and the scalar outputs.  Each
         distinct (source, selector) is gathered once; keys the reference
         computes by the same expression share the tensor."""
-        torch = _torch()
-        ds = self.dataset
-        out, cols, vcols, mcols, made = {}, [], [], [], {}
-
-        def add(src_key, dst_key, select):
-            spec = self._visual_spec(src_key, dst_key)
-            dst = made.get((src_key, select, spec))
-            if dst is None:
-                if spec is not None:
-                    # the midpoint's image columns go to a gather of their own,
-                    # which reads value_midpoint_idxs as its idxs (selector 0)
-                    mid = select == TRL_SELECT_MIDPOINT
-                    dst, vc = self._vcolumn(src_key, 0 if mid else select, spec, total)
-                    (mcols if mid else vcols).append(vc)
-                else:
-                    src = ds[src_key]
-                    dst = torch.empty((total,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
-                    cols.append(self._column(src_key, dst, select))
-                made[(src_key, select, spec)] = dst
-            out[dst_key] = dst
-
-        def scalar(dtype):
-            return torch.empty(total, dtype=dtype, device=self.device)
-
-        i64, f64 = torch.int64, torch.float64
-        for k in ds.keys():
-            add(k, k, 0)
-        if 'next_observations' not in ds:
-            add('observations', 'next_observations', 1)
-        goal_src = 'oracle_reps' if 'oracle_reps' in ds else 'observations'
-        add(goal_src, 'value_goals', 2)
-        add(goal_src, 'actor_goals', 3)
-        out['masks'], out['rewards'] = scalar(f64), scalar(f64)
-        add('observations', 'value_goal_observations', 2)
-        add('observations', 'actor_goal_observations', 2)  # the value goal, as the reference (datasets.py:262)
-        out['value_offsets'], out['value_midpoint_offsets'] = scalar(i64), scalar(i64)
-        add('observations', 'value_midpoint_observations', TRL_SELECT_MIDPOINT)
-        add('actions', 'value_midpoint_actions', TRL_SELECT_MIDPOINT)
-        add('actions', 'next_actions', 1)
-        add(goal_src, 'value_midpoint_goals', TRL_SELECT_MIDPOINT)
-        add(goal_src, 'value_cur_goals', 0)
-        add(goal_src, 'value_next_goals', 1)
-        # index outputs only when something reads them (the gathers of a visual batch, a recording call)
-        idx_t = {'_' + k: scalar(i64) for k in (_TRL_SCALARS[:4] if (record or self._visual) else ())}
-        bad = torch.zeros(1, dtype=i64, device=self.device) if checked else None
-        outs = TrlOutputs(*[_lib.ptr(idx_t.get('_' + k)) for k in _TRL_SCALARS[:4]],
-                          *[out[k].data_ptr() for k in _TRL_SCALARS[4:8]], _lib.ptr(bad))
+        vcols, mcols = ([], []) if self._visual else (None, None)
+        out, cols, outs, idx_t, bad = self._trl_walk(total, record, checked, vcols, mcols)
+        vcols, mcols = vcols or (), mcols or ()
         col_keep = (GcColumn * max(1, len(cols)))(*cols)
         vcol_keep = (VisualColumn * max(1, len(vcols)))(*vcols)
         mcol_keep = (VisualColumn * max(1, len(mcols)))(*mcols)
         vidx = midx = None
         if self._visual:
-            vidx = VisualIndices(idx_t['_idxs'].data_ptr(), idx_t['_value_goal_idxs'].data_ptr(),
-                                 idx_t['_actor_goal_idxs'].data_ptr(), None)
+            vidx = self._visual_indices(idx_t)
             midx = VisualIndices(idx_t['_value_midpoint_idxs'].data_ptr(), None, None, None)
         return (out, ctypes.cast(col_keep, ctypes.c_void_p), len(cols), outs,
                 ctypes.cast(vcol_keep, ctypes.c_void_p), len(vcols), vidx,
@@ -1162,20 +1290,13 @@ class GCDataset:
                 or (self._rec_src and tuple(map(_VERSION, self._rec_tensors)) != self._rec_versions)):
             self._refresh_record()
             self._trl_cache.clear()
-        # the coin of datasets.py:278-279, on the host; the offsets are device draws
+        # a non-visual sampler crops nothing; its coin is drawn after the launch, below
         crop = bool(self._visual and self._p_aug_live and not evaluation and np.random.rand() < self._p_aug)
         draws = dict(draws or {})
         crop_from = draws.pop('crop_from', None)
         midpoint = draws.pop('midpoint', None)
-        cf = mid_in = None
-        if crop and crop_from is not None:
-            cf = _to_device(crop_from, self.device).to(torch.int64)
-            if tuple(cf.shape) != (total, 2):
-                raise ValueError(f"draws['crop_from'] must have shape ({total}, 2), got {tuple(cf.shape)}")
-        if midpoint is not None:
-            mid_in = _to_device(midpoint, self.device).to(torch.int64).reshape(-1)
-            if mid_in.numel() != total:
-                raise ValueError(f"draws['midpoint'] must have {total} entries, got {mid_in.numel()}")
+        cf = self._stage_crop_from(crop_from, total) if (crop and crop_from is not None) else None
+        mid_in = self._stage_midpoint(midpoint, total) if midpoint is not None else None
         # explicit idxs or injected draws may put a value goal at or before its
         # sample: such a call has the kernel count those samples and reads the
         # count back (one sync); Philox draws on the pick table cannot
@@ -1187,9 +1308,7 @@ class GCDataset:
         else:
             st = self._trl_batch(total, record_draws, checked)
             if plain_call:
-                if len(self._trl_cache) >= 2:
-                    self._trl_cache.clear()
-                self._trl_cache[id(st[0])] = (st[0], (B, nb), st)
+                self._remember(self._trl_cache, st[0], (B, nb), st)
         out, col_arr, ncols, outs, vcol_arr, nvcols, vidx, mcol_arr, nmcols, midx, idx_t, bad, _ = st
         dr, staged, rec, rec_t = self._stage(total, idxs, draws, record_draws)
         mid_rec = torch.empty(total, dtype=torch.int64, device=self.device) if record_draws else None
@@ -1213,16 +1332,9 @@ class GCDataset:
             np.random.rand()  # the coin; nothing of a non-visual batch is cropped
         del staged, cf, mid_in  # alive until the launches were issued
         if bad is not None:
-            n = int(bad.item())
-            if n:
-                raise ValueError(f'trl_sample: {n} of {total} samples have no row between the sample and its value '
-                                 f'goal (an index names the last row of its trajectory, or the injected draws put '
-                                 f'the value goal at or before the sample)')
+            self._check_bad(bad, total, 'trl_sample')
         if record_draws:
-            rec_t['midpoint'] = mid_rec
-            if cf_out is not None:
-                rec_t['crop_from'] = cf_out
-            out.update({'_draws': rec_t, **idx_t})
+            out.update(self._recorded(rec_t, idx_t, midpoint=mid_rec, crop_from=cf_out))
         return out
 
     def _sample_new(self, B, nb, idxs, draws, record_draws, keys, plain_call, shape):
@@ -1244,9 +1356,7 @@ class GCDataset:
             _lib.check(self._set_batch(plan, slot, col_arr, len(cols), B, nb, scalars), 'gc_plan_set_batch')
             # remember the batch's plan slot so that sample(..., out=this) skips
             # setup (the output tensors stay alive in `out` and `keep`)
-            if len(self._out_cache) >= 2:
-                self._out_cache.clear()
-            self._out_cache[id(out)] = (out, shape, slot, keep)
+            self._remember(self._out_cache, out, shape, slot, keep)
             st = self._L.ogbx_gc_plan_sample(plan, slot, call, stream)
         else:
             st = self._direct(col_arr, len(cols), B, nb, dr, seed, call, scalars, rec, stream)
@@ -1254,7 +1364,7 @@ class GCDataset:
         del staged, col_keep  # alive until the launch was issued
         if not record_draws or self._plain:
             return out, None
-        return out, {'_draws': rec_t, **idx_t}
+        return out, self._recorded(rec_t, idx_t)
 
 
 # ----------------------------------------------------------------------------- HGCDataset
@@ -1374,7 +1484,75 @@ def _subgoal_tables(discount, K, gc_negative, device):
             torch.as_tensor(np.ascontiguousarray(rewards, dtype=np.float64), device=device))
 
 
-class HGCDataset(GCDataset):
+class _HgcHost:
+    """What the hierarchical samplers (``HGCDataset``, ``HGCReplayBuffer``)
+    put in place of ``_SamplerHost``'s hooks: the subgoal steps, tables and
+    ``HgcConfig`` of a config, the image keys, the ``l_*`` draws and the walk
+    that lays an HGC batch out."""
+
+    _VISUAL_KEYS = ('observations', 'next_observations', 'high_value_reps', 'high_value_goals', 'high_value_actions',
+                    'high_value_next_observations', 'low_value_next_observations', 'low_value_goals',
+                    'high_actor_goals', 'high_actor_actions', 'high_actor_next_observations', 'low_actor_goals',
+                    'low_actor_goal_observations', 'low_actor_next_observations')
+    _CROP_KEYS = tuple(k for k in _VISUAL_KEYS if k not in ('high_value_reps', 'low_value_goals'))
+    _TRL_OK = False
+
+    def _init_hgc(self, config):
+        """The subgoal steps as the reference resolves them
+        (datasets.py:467-494), the mask / reward tables and ``_hcfg``."""
+        c = config
+        high = c.get('high_subgoal_steps', c['subgoal_steps'])
+        self.value_subgoal_steps = int(high if c.get('value_subgoal_steps') is None else c['value_subgoal_steps'])
+        self.actor_subgoal_steps = int(high if c.get('actor_subgoal_steps') is None else c['actor_subgoal_steps'])
+        self.low_subgoal_steps = int(c.get('low_subgoal_steps', c['subgoal_steps']))
+        self._has_low = c.get('low_discount') is not None
+        self._draw_keys = _DRAW_ORDER + (_HDRAW_LOW if self._has_low else ())
+        self._hv_tab = _subgoal_tables(c['discount'], self.value_subgoal_steps, c['gc_negative'], self.device)
+        self._lv_tab = _subgoal_tables(c['discount'], self.low_subgoal_steps, c['gc_negative'], self.device)
+        self._hcfg = HgcConfig(
+            self.value_subgoal_steps, self.low_subgoal_steps, self.actor_subgoal_steps, int(self._has_low), 0,
+            float(c['low_discount']) if self._has_low else 0.0,
+            self._hv_tab[0].data_ptr(), self._hv_tab[1].data_ptr(),
+            self._lv_tab[0].data_ptr(), self._lv_tab[1].data_ptr(),
+        )
+
+    def _hcfg_ptr(self):
+        return ctypes.byref(self._hcfg)
+
+    def _visual_indices(self, idx_t):
+        return VisualIndices(*[idx_t['_' + k].data_ptr() for k in _HGC_SCALARS[:4]])
+
+    def _draw_structs(self):
+        dr = HgcDraws()
+        return dr, dr.gc
+
+    def _record_struct(self, rec_t):
+        # the l_* draws exist (and are recorded) only with low_discount
+        return HgcDrawRecord(super()._record_struct(rec_t), *[_lib.ptr(rec_t.get(k)) for k in _HDRAW_LOW])
+
+    def _hgc_walk(self, total, record, vcols=None):
+        """A new HGC batch: the data's own keys, then ``_HGC_LAYOUT``
+        (``_hgc_outputs``).  Returns the batch in the reference's key order,
+        the fused columns' descriptors (image columns go to ``vcols``),
+        ``HgcOutputs`` and the index outputs of a recording call."""
+        torch = _torch()
+        out, cols = {}, []
+        for src_key, key, select in self._own_columns():
+            out[key] = self._gather(src_key, key, select, total, cols, vcols)
+        if vcols is not None:
+            # a visual batch's observations may be cropped; high_value_reps never is
+            out['high_value_reps'] = self._gather('observations', 'high_value_reps', 0, total, cols, vcols)
+        for key, src_key, select in _hgc_outputs(out, total, self._goal_source(), self._has_low, self.device,
+                                                 own_reps=vcols is not None):
+            out[key] = self._gather(src_key, key, select, total, cols, vcols)
+        idx_t = {k: torch.empty(total, dtype=torch.int64, device=self.device)
+                 for k in (_HGC_SCALARS[:4] if record else ())}
+        outs = HgcOutputs(*[_lib.ptr(idx_t.get(k)) for k in _HGC_SCALARS[:4]],
+                          *[out[k].data_ptr() for k in _HGC_SCALARS[4:]])
+        return out, cols, outs, {'_' + k: t for k, t in idx_t.items()}
+
+
+class HGCDataset(_HgcHost, GCDataset):
     """Hierarchical goal-conditioned sampler (reference: datasets.py:467-643).
 
     Extra config keys (as the reference): subgoal_steps, optional
@@ -1390,90 +1568,19 @@ class HGCDataset(GCDataset):
     them) and ``low_value_goals`` (not in the list) stay uncropped.
     """
 
-    _VISUAL_KEYS = ('observations', 'next_observations', 'high_value_reps', 'high_value_goals', 'high_value_actions',
-                    'high_value_next_observations', 'low_value_next_observations', 'low_value_goals',
-                    'high_actor_goals', 'high_actor_actions', 'high_actor_next_observations', 'low_actor_goals',
-                    'low_actor_goal_observations', 'low_actor_next_observations')
-    _CROP_KEYS = tuple(k for k in _VISUAL_KEYS if k not in ('high_value_reps', 'low_value_goals'))
-    _TRL_OK = False
-
-    def _hcfg_ptr(self):
-        return ctypes.byref(self._hcfg)
-
     def __init__(self, dataset, config, preprocess_frame_stack=True, seed=None):
         super().__init__(dataset, config, preprocess_frame_stack=preprocess_frame_stack, seed=seed)
-        c = config
-        high = c.get('high_subgoal_steps', c['subgoal_steps'])
-        self.value_subgoal_steps = int(high if c.get('value_subgoal_steps') is None else c['value_subgoal_steps'])
-        self.actor_subgoal_steps = int(high if c.get('actor_subgoal_steps') is None else c['actor_subgoal_steps'])
-        self.low_subgoal_steps = int(c.get('low_subgoal_steps', c['subgoal_steps']))
-        self._has_low = c.get('low_discount') is not None
-        self._draw_keys = _DRAW_ORDER + (_HDRAW_LOW if self._has_low else ())
-        dev = self.device
-        self._hv_tab = _subgoal_tables(c['discount'], self.value_subgoal_steps, c['gc_negative'], dev)
-        self._lv_tab = _subgoal_tables(c['discount'], self.low_subgoal_steps, c['gc_negative'], dev)
-        self._hcfg = HgcConfig(
-            self.value_subgoal_steps, self.low_subgoal_steps, self.actor_subgoal_steps, int(self._has_low), 0,
-            float(c['low_discount']) if self._has_low else 0.0,
-            self._hv_tab[0].data_ptr(), self._hv_tab[1].data_ptr(),
-            self._lv_tab[0].data_ptr(), self._lv_tab[1].data_ptr(),
-        )
+        self._init_hgc(config)
         self._Lh = _bind_hgc()
 
-    def _hcolumns(self, total, vcols=None):
-        """Output tensors in the reference's key order, and column descriptors
-        (the image columns of a visual sampler go to ``vcols``)."""
-        torch = _torch()
-        ds = self.dataset
-        out, cols = {}, []
-        goal_src = 'oracle_reps' if 'oracle_reps' in ds else 'observations'
-
-        def col(src_key, select, key=None):
-            spec = self._visual_spec(src_key, key) if vcols is not None else None
-            if spec is not None:
-                dst, vc = self._vcolumn(src_key, select, spec, total)
-                vcols.append(vc)
-                return dst
-            src = ds[src_key]
-            dst = torch.empty((total,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
-            cols.append(self._column(src_key, dst, select))
-            return dst
-
-        for k in ds.keys():
-            out[k] = col(k, 0, k)
-        if 'next_observations' not in ds:
-            out['next_observations'] = col('observations', 1, 'next_observations')
-        if vcols is not None:
-            # a visual batch's observations may be cropped; high_value_reps never is
-            out['high_value_reps'] = col('observations', 0, 'high_value_reps')
-        for key, src_key, select in _hgc_outputs(out, total, goal_src, self._has_low, self.device,
-                                                 own_reps=vcols is not None):
-            out[key] = col(src_key, select, key)
-        return out, cols
-
-    # sample() is GCDataset's; what differs for the hierarchical sampler:
+    # sample() is GCDataset's; what differs for the hierarchical sampler
+    # (with the hooks of _HgcHost):
     _what = 'hgc_sample'
 
-    def _visual_indices(self, idx_t):
-        return VisualIndices(*[idx_t['_' + k].data_ptr() for k in _HGC_SCALARS[:4]])
-
     def _batch(self, total, keys, record, vcols=None):
-        torch = _torch()
         assert keys is None
-        out, cols = self._hcolumns(total, vcols)
-        idx_t = {k: torch.empty(total, dtype=torch.int64, device=self.device)
-                 for k in (_HGC_SCALARS[:4] if record else ())}
-        outs = HgcOutputs(*[_lib.ptr(idx_t.get(k)) for k in _HGC_SCALARS[:4]],
-                          *[out[k].data_ptr() for k in _HGC_SCALARS[4:]])
-        return out, cols, outs, (), {'_' + k: t for k, t in idx_t.items()}
-
-    def _draw_structs(self):
-        dr = HgcDraws()
-        return dr, dr.gc
-
-    def _record_struct(self, rec_t):
-        # the l_* draws exist (and are recorded) only with low_discount
-        return HgcDrawRecord(super()._record_struct(rec_t), *[_lib.ptr(rec_t.get(k)) for k in _HDRAW_LOW])
+        out, cols, outs, idx_t = self._hgc_walk(total, record, vcols)
+        return out, cols, outs, (), idx_t
 
     def _set_batch(self, plan, slot, col_arr, ncols, B, nb, outs):
         return self._Lh.ogbx_gc_plan_set_batch(plan, slot, col_arr, ncols, B, nb, None, None, None, None, None,
@@ -1731,13 +1838,11 @@ def _replay_dtypes():
     return {torch.bool: 0, torch.uint8: 1, torch.int32: 2, torch.int64: 3, torch.float32: 4, torch.float64: 5}
 
 
-class _BufferHost:
+class _BufferHost(_CallHost):
     """The host side that ``ReplayBuffer`` and the ring buffers share (each is
     also a ``Dataset`` of device columns): staging of what an insert takes, the
     cached insert descriptors, the descriptor of a gathered column and the
-    ``out=`` cache."""
-
-    _next_seed = GCDataset._next_seed
+    ``out=`` cache (``_out_cache``, emptied when a column was replaced)."""
 
     def _init_host(self, seed):
         self._L = _bind()
@@ -1831,16 +1936,6 @@ class _BufferHost:
         dst = self._new((B,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
         row_bytes = (src[0].numel() if src.dim() > 1 else 1) * src.element_size()
         return dst, GcColumn(src.data_ptr(), dst.data_ptr(), row_bytes, select, 0)
-
-    # The out= cache: the last two batches that plain calls returned, by
-    # id(out), each with its shape and what a refill passes on; emptied when a
-    # column was replaced.  A steady refill is host-bound, so the
-    # lookup and the refill's one ctypes call stand in line in each sample(),
-    # not behind a call of their own; only a new batch comes through here.
-    def _out_remember(self, out, shape, held):
-        if len(self._out_cache) >= 2:
-            self._out_cache.clear()
-        self._out_cache[id(out)] = (out, shape, held)
 
 
 class ReplayBuffer(_BufferHost, Dataset):
@@ -2130,7 +2225,7 @@ class ReplayBuffer(_BufferHost, Dataset):
         else:
             out, arr, ncols, idx_out = self._batch(B, record_idxs)
             if ix is None:
-                self._out_remember(out, (B, record_idxs), (arr, ncols, idx_out))
+                self._remember(self._out_cache, out, (B, record_idxs), (arr, ncols, idx_out))
         seed, call = self._next_seed()
         st = self._L.ogbx_replay_sample(self._hdr.data_ptr(), self._parity, self.max_size, arr, ncols, B,
                                         _lib.ptr(ix), seed, call, _lib.ptr(idx_out), self._empty.data_ptr(),
@@ -2147,7 +2242,7 @@ class ReplayBuffer(_BufferHost, Dataset):
         return self.sample(num_idxs, record_idxs=True)['_idxs']
 
 
-class GCReplayBuffer(_BufferHost, Dataset):
+class GCReplayBuffer(_SamplerHost, _BufferHost, Dataset):
     """Hindsight goal sampling over an on-device episode ring: what batched
     envs produce, one row per env and step, sampled as the reference's
     ``GCDataset.sample`` (datasets.py:213-327) samples a dataset
@@ -2254,13 +2349,9 @@ class GCReplayBuffer(_BufferHost, Dataset):
 
     RESERVED = ('masks', 'rewards', 'value_goals', 'actor_goals', 'valids')
     STEP_KEYS = ('observations', 'actions', 'next_observations', 'terminals')
-    # GCDataset's rules for the image keys (_visual_spec reads the columns
-    # through ``dataset``: for a ring, the buffer itself)
-    _VISUAL_KEYS = GCDataset._VISUAL_KEYS
-    _CROP_KEYS = GCDataset._CROP_KEYS
-    _visual_spec = GCDataset._visual_spec
-    _visual_indices = GCDataset._visual_indices
+    # _SamplerHost reads the columns through ``dataset``: for a ring, the buffer itself
     dataset = property(lambda self: self)
+    _VisualColumn = OnlineVisualColumn  # ogbx_online_visual_gather's descriptor
 
     @classmethod
     def create(cls, transition, num_envs, horizon, config, device=None, seed=None):
@@ -2404,47 +2495,31 @@ class GCReplayBuffer(_BufferHost, Dataset):
         self._insert(specs, done, done if alt is not None else None)
 
     # ----------------------------------------------------------------- sampling
-    def _vcolumn(self, src_key, dst_key, select, spec, B):
-        """(destination, descriptor) of one image column (GCDataset._vcolumn
-        for the ring).  A stacked ``next_observations`` is the stack over
-        ``observations`` with the buffer's own row as its newest block."""
-        stack, crop = spec
+    def _gather(self, src_key, dst_key, select, B, cols, vcols):
+        """The destination of one output column.  Its descriptor goes to
+        ``vcols`` when it is an image column of a visual buffer, else to
+        ``cols`` (the sample kernel's).  A stacked ``next_observations`` is the
+        stack over ``observations`` with the buffer's own row as its newest
+        block (``alt``)."""
+        spec = self._visual_spec(src_key, dst_key) if vcols is not None else None
+        if spec is None:
+            dst, col = self._gather_column(src_key, B, select, self.rows)
+            cols.append(col)
+            return dst
         alt = None
-        if dst_key == 'next_observations' and src_key == 'next_observations' and stack:
+        if dst_key == 'next_observations' and src_key == 'next_observations' and spec[0]:
             alt, src_key = self._column_of('next_observations', self.rows), 'observations'
         src = self._column_of(src_key, self.rows)
         if alt is not None and (alt.shape != src.shape or alt.dtype != src.dtype):
             raise ValueError("frame_stack needs 'next_observations' of the shape and dtype of 'observations'")
-        shape = tuple(src.shape[1:])
-        F = self._frame_stack if stack else 1
-        dst = self._new((B,) + shape[:-1] + (shape[-1] * F,), dtype=src.dtype, device=self.device)
-        # an image is [H, W, C]; any other row is a 1-row image of its leading elements
-        H, W = (shape[0], shape[1]) if len(shape) == 3 else (1, int(np.prod(shape[:-1], dtype=np.int64)))
-        return dst, OnlineVisualColumn(src.data_ptr(), alt.data_ptr() if alt is not None else None, dst.data_ptr(),
-                                       H, W, shape[-1] * src.element_size(), select, int(stack), int(crop))
-
-    def _gather(self, src_key, dst_key, select, B, cols, vcols):
-        """The destination of one output column; its descriptor goes to
-        ``vcols`` when it is an image column of a visual buffer, else to
-        ``cols`` (the sample kernel's)."""
-        spec = self._visual_spec(src_key, dst_key) if vcols is not None else None
-        if spec is not None:
-            dst, vc = self._vcolumn(src_key, dst_key, select, spec, B)
-            vcols.append(vc)
-        else:
-            dst, col = self._gather_column(src_key, B, select, self.rows)
-            cols.append(col)
+        dst, vc = self._image_column(src, (src.data_ptr(), alt.data_ptr() if alt is not None else None), select, spec,
+                                     B)
+        vcols.append(vc)
         return dst
 
     def _batch(self, B, record, vcols=None):
         torch = _torch()
-        out, cols = {}, []
-
-        goal_src = 'oracle_reps' if 'oracle_reps' in self else 'observations'  # datasets.py:348-357
-        for k in self.keys():
-            out[k] = self._gather(k, k, 0, B, cols, vcols)
-        for dst_key, select in (('value_goals', 2), ('actor_goals', 3)):
-            out[dst_key] = self._gather(goal_src, dst_key, select, B, cols, vcols)
+        out, cols = self._gc_walk(B, vcols)
         if len(cols) > REPLAY_MAX_COLS:
             raise ValueError(f'at most {REPLAY_MAX_COLS} columns per sample, got {len(cols)}')
         out['masks'] = torch.empty(B, dtype=torch.float64, device=self.device)
@@ -2512,10 +2587,9 @@ class GCReplayBuffer(_BufferHost, Dataset):
         if plain:
             # a refill's leading arguments (a plain call has neither draws nor
             # a record), and what keeps the descriptors alive
-            self._out_remember(out, B, (args, held))
+            self._remember(self._out_cache, out, B, (args, held))
         if record_draws:
-            out['_draws'] = rec_t
-            out.update(idx_t)
+            out.update(self._recorded(rec_t, idx_t))
         return out
 
     def _sample_visual(self, batch_size, idxs=None, draws=None, record_draws=False, out=None, evaluation=False):
@@ -2528,15 +2602,10 @@ class GCReplayBuffer(_BufferHost, Dataset):
         B = int(batch_size)
         if self._steps == 0:
             raise ValueError(f'cannot sample from an empty {self._NAME}')
-        # the coin stays on the host (datasets.py:278-279); the offsets are device draws
         crop = bool(self._p_aug_live and not evaluation and np.random.rand() < self._p_aug)
         draws = dict(draws or {})
         crop_from = draws.pop('crop_from', None)
-        cf = None
-        if crop and crop_from is not None and self._visual:
-            cf = _to_device(crop_from, self.device).to(torch.int64)
-            if tuple(cf.shape) != (B, 2):
-                raise ValueError(f"draws['crop_from'] must have shape ({B}, 2), got {tuple(cf.shape)}")
+        cf = self._stage_crop_from(crop_from, B) if (crop and crop_from is not None and self._visual) else None
         plain = idxs is None and not draws and crop_from is None and not record_draws
         if self._out_gen != self._gen:  # a column was replaced
             self._vis_cache.clear()
@@ -2555,9 +2624,7 @@ class GCReplayBuffer(_BufferHost, Dataset):
             varr = (OnlineVisualColumn * max(1, nv))(*(vcols or ()))
             st = (held, varr, nv, self._visual_indices(idx_t), idx_t)
             if plain:
-                if len(self._vis_cache) >= 2:
-                    self._vis_cache.clear()
-                self._vis_cache[id(out)] = (out, B, st)
+                self._remember(self._vis_cache, out, B, st)
         held, varr, nv, vidx, idx_t = st
         dr, staged, rec, rec_t = self._stage(B, idxs, draws, record_draws)
         seed, call = self._next_seed()
@@ -2572,17 +2639,12 @@ class GCReplayBuffer(_BufferHost, Dataset):
                 int(crop and cf is None), seed, call, _lib.ptr(cf_out), stream), 'online_visual_gather')
         del staged, cf  # alive until the launches were issued
         if record_draws:
-            if cf_out is not None:
-                rec_t['crop_from'] = cf_out
-            out['_draws'] = rec_t
-            out.update(idx_t)
+            out.update(self._recorded(rec_t, idx_t, crop_from=cf_out))
         return out
 
     # --------------------------------------------------------------- TRL batches
-    _TRL_OK = True  # the reference's GCDataset.sample has the TRL branch; HGCDataset.sample has none
-    _TRL_KEYS = ('value_goal_observations', 'actor_goal_observations', 'value_offsets', 'value_midpoint_offsets',
-                 'value_midpoint_observations', 'value_midpoint_actions', 'next_actions', 'value_midpoint_goals',
-                 'value_cur_goals', 'value_next_goals')  # datasets.py:261-276
+    # what the TRL branch adds (datasets.py:261-276) to the four RESERVED keys of a GC batch
+    _TRL_KEYS = tuple(k for k, _, _ in _TRL_LAYOUT[4:])
 
     def _init_trl(self):
         """What a buffer with a TRL agent name adds at construction: the
@@ -2619,47 +2681,10 @@ class GCReplayBuffer(_BufferHost, Dataset):
         return int(self._trl_bad.item())
 
     def _trl_batch(self, B, record, checked):
-        """A new TRL batch (``GCDataset._trl_batch`` for the ring): the output
-        dict in the reference's key order (datasets.py:228-276), the
-        descriptors of its columns (selectors 0..4) and the scalar outputs.
-        Each distinct (source, selector) is gathered once; keys the reference
-        computes by the same expression share the tensor."""
-        torch = _torch()
-        out, cols, made = {}, [], {}
-
-        def add(src_key, dst_key, select):
-            dst = made.get((src_key, select))
-            if dst is None:
-                dst, col = self._gather_column(src_key, B, select, self.rows)
-                cols.append(col)
-                made[(src_key, select)] = dst
-            out[dst_key] = dst
-
-        def scalar(dtype):
-            return torch.empty(B, dtype=dtype, device=self.device)
-
-        i64, f64 = torch.int64, torch.float64
-        for k in self.keys():
-            add(k, k, 0)
-        goal_src = 'oracle_reps' if 'oracle_reps' in self else 'observations'  # datasets.py:348-357
-        add(goal_src, 'value_goals', 2)
-        add(goal_src, 'actor_goals', 3)
-        out['masks'], out['rewards'] = scalar(f64), scalar(f64)
-        add('observations', 'value_goal_observations', 2)
-        add('observations', 'actor_goal_observations', 2)  # the value goal, as the reference (datasets.py:262)
-        out['value_offsets'], out['value_midpoint_offsets'] = scalar(i64), scalar(i64)
-        add('observations', 'value_midpoint_observations', TRL_SELECT_MIDPOINT)
-        add('actions', 'value_midpoint_actions', TRL_SELECT_MIDPOINT)
-        add('actions', 'next_actions', 1)  # the snapshot's actions[idxs + 1]
-        add(goal_src, 'value_midpoint_goals', TRL_SELECT_MIDPOINT)
-        add(goal_src, 'value_cur_goals', 0)
-        add(goal_src, 'value_next_goals', 1)  # the snapshot's row idxs + 1, not the buffer's next_observations
-        idx_t = {'_' + k: scalar(i64) for k in (_TRL_SCALARS[:4] if record else ())}
-        # a checked call counts into a counter of its own and reads it back
-        bad = torch.zeros(1, dtype=i64, device=self.device) if checked else None
-        outs = TrlOutputs(*[_lib.ptr(idx_t.get('_' + k)) for k in _TRL_SCALARS[:4]],
-                          *[out[k].data_ptr() for k in _TRL_SCALARS[4:8]],
-                          (bad if checked else self._trl_bad).data_ptr())
+        """A new TRL batch (``_trl_walk``): the output dict, what a refill
+        passes on (the column descriptors, selectors 0..4, and the scalar
+        outputs), the index outputs and the counter of a checked call."""
+        out, cols, outs, idx_t, bad = self._trl_walk(B, record, checked)
         arr = (GcColumn * len(cols))(*cols)  # at most 14 columns of the buffer and 8 further gathers
         return out, (arr, len(cols), outs), idx_t, bad
 
@@ -2683,15 +2708,8 @@ class GCReplayBuffer(_BufferHost, Dataset):
                              f'trajectory, so no row can be picked')
         draws = dict(draws or {})
         midpoint = draws.pop('midpoint', None)
-        mid_in = None
-        if midpoint is not None:
-            mid_in = _to_device(midpoint, self.device).to(torch.int64).reshape(-1)
-            if mid_in.numel() != B:
-                raise ValueError(f"draws['midpoint'] must have {B} entries, got {mid_in.numel()}")
-        # explicit idxs or injected draws may put a value goal at or before its
-        # sample: such a call has the kernel count those samples and reads the
-        # count back (one sync); Philox draws on the pick table cannot
-        checked = idxs is not None or bool(draws) or mid_in is not None
+        mid_in = self._stage_midpoint(midpoint, B) if midpoint is not None else None
+        checked = idxs is not None or bool(draws) or mid_in is not None  # as GCDataset._sample_trl
         plain = not checked and not record_draws
         if self._out_gen != self._gen:  # a column was replaced
             self._out_cache.clear()
@@ -2705,7 +2723,7 @@ class GCReplayBuffer(_BufferHost, Dataset):
                 raise ValueError(f"out= holds a batch of {len(out['masks'])} samples, not {B}")
             out, held, idx_t, bad = self._trl_batch(B, record_draws, checked)
             if plain:
-                self._out_remember(out, B, held)
+                self._remember(self._out_cache, out, B, held)
         arr, ncols, outs = held
         dr, staged, rec, rec_t = self._stage(B, idxs, draws, record_draws)
         mid_rec = torch.empty(B, dtype=torch.int64, device=self.device) if record_draws else None
@@ -2723,70 +2741,20 @@ class GCReplayBuffer(_BufferHost, Dataset):
                    'online_trl_sample')
         del staged, mid_in  # alive until the launch was issued
         if bad is not None:
-            n = int(bad.item())
-            if n:
-                raise ValueError(f'online_trl_sample: {n} of {B} samples have no row between the sample and its '
-                                 f'value goal (an index names the last row of its trajectory, or the injected draws '
-                                 f'put the value goal at or before the sample)')
+            self._check_bad(bad, B, 'online_trl_sample')
         if record_draws:
-            rec_t['midpoint'] = mid_rec
-            out.update({'_draws': rec_t, **idx_t})
+            out.update(self._recorded(rec_t, idx_t, midpoint=mid_rec))
         return out
-
-    def _hcfg_ptr(self):
-        return None  # HGCReplayBuffer passes its ogbx_hgc_config
 
     # ------------------------------------- what HGCReplayBuffer supplies instead
     # (with _batch; the hook names of GCDataset / HGCDataset where they match)
     _NAME = 'GCReplayBuffer'  # names the class in sample()'s message
     _what = 'online_gc_sample'  # names the call in error messages
-    _draw_keys = _DRAW_ORDER  # the draws a call takes and a recording call reports
-
-    def _draw_structs(self):
-        """(injected draws to fill, its GC part)."""
-        dr = GcDraws()
-        return dr, dr
-
-    def _record_struct(self, rec_t):
-        return GcDrawRecord(*[rec_t[k].data_ptr() for k in _DRAW_ORDER])
 
     def _sample_args(self, held, dr, rec):
         """The arguments of ``_sample_entry`` before (seed, call, stream), from
         what ``_batch`` returned second."""
         return self._ring, self._cfg, held[0], dr, rec
-
-    def _stage(self, B, idxs, draws, record_draws):
-        """``GCDataset._stage`` for the ring: explicit idxs and injected draws
-        on the device and the record buffers of a recording call -- (draws
-        struct or None, tensors to keep alive until the launch was issued,
-        record struct or None, its tensors or None).  A wrong length or a draw
-        the sampler does not take raises ValueError."""
-        torch = _torch()
-        dr = rec = rec_t = None
-        staged = []
-        if idxs is not None or draws:
-            dr, gdr = self._draw_structs()
-            if idxs is not None:
-                t = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
-                if t.numel() != B:
-                    raise ValueError(f'idxs must have {B} entries, got {t.numel()}')
-                staged.append(t)
-                gdr.idxs = t.data_ptr()
-            for k, v in (draws or {}).items():
-                if k == 'idxs':
-                    continue
-                if k not in self._draw_keys:
-                    raise ValueError(f'unknown draw {k!r}')
-                t = _to_device(v, self.device).to(torch.int64 if k in _HDRAW_INT else torch.float64).reshape(-1)
-                if t.numel() != B:
-                    raise ValueError(f'draw {k!r} must have {B} entries, got {t.numel()}')
-                staged.append(t)
-                setattr(dr if k in _HDRAW_LOW else gdr, k, t.data_ptr())
-        if record_draws:
-            rec_t = {k: torch.empty(B, dtype=torch.int64 if k in _HDRAW_INT else torch.float64, device=self.device)
-                     for k in self._draw_keys}
-            rec = self._record_struct(rec_t)
-        return dr, staged, rec, rec_t
 
     def get_subset(self, idxs):
         return self.sample(len(idxs), idxs=idxs)
@@ -2816,7 +2784,7 @@ class GCReplayBuffer(_BufferHost, Dataset):
         return Dataset(data, device=self.device)
 
 
-class HGCReplayBuffer(GCReplayBuffer):
+class HGCReplayBuffer(_HgcHost, GCReplayBuffer):
     """Hierarchical hindsight sampling over the episode ring of
     ``GCReplayBuffer``: the same constructor, inserts, ``clear``, ``snapshot``
     and state, and a ``sample`` that returns what the reference's
@@ -2855,68 +2823,21 @@ class HGCReplayBuffer(GCReplayBuffer):
     def __init__(self, data, num_envs, horizon, config, device=None, seed=None):
         super().__init__(data, num_envs, horizon, config, device=device, seed=seed)
         self._sample_entry = self._L.ogbx_online_hgc_sample
-        c = config
-        high = c.get('high_subgoal_steps', c['subgoal_steps'])
-        self.value_subgoal_steps = int(high if c.get('value_subgoal_steps') is None else c['value_subgoal_steps'])
-        self.actor_subgoal_steps = int(high if c.get('actor_subgoal_steps') is None else c['actor_subgoal_steps'])
-        self.low_subgoal_steps = int(c.get('low_subgoal_steps', c['subgoal_steps']))
+        self._init_hgc(config)
         if min(self.value_subgoal_steps, self.actor_subgoal_steps, self.low_subgoal_steps) < 1:
             raise ValueError('subgoal steps must be >= 1')
-        self._has_low = c.get('low_discount') is not None
-        self._draw_keys = _DRAW_ORDER + (_HDRAW_LOW if self._has_low else ())
-        self._hv_tab = _subgoal_tables(c['discount'], self.value_subgoal_steps, c['gc_negative'], self.device)
-        self._lv_tab = _subgoal_tables(c['discount'], self.low_subgoal_steps, c['gc_negative'], self.device)
-        self._hcfg = HgcConfig(
-            self.value_subgoal_steps, self.low_subgoal_steps, self.actor_subgoal_steps, int(self._has_low), 0,
-            float(c['low_discount']) if self._has_low else 0.0,
-            self._hv_tab[0].data_ptr(), self._hv_tab[1].data_ptr(),
-            self._lv_tab[0].data_ptr(), self._lv_tab[1].data_ptr(),
-        )
 
-    # ----------------------------------------------------------------- sampling
-    def _batch(self, B, record, vcols=None):
-        """Output tensors in the reference's key order (HGCDataset._hcolumns),
-        the column descriptors (the image columns of a visual buffer go to
-        ``vcols``) and the scalar outputs."""
-        torch = _torch()
-        out, cols = {}, []
-
-        for k in self.keys():
-            out[k] = self._gather(k, k, 0, B, cols, vcols)
-        if vcols is not None:
-            # a visual batch's observations may be cropped; high_value_reps never is
-            out['high_value_reps'] = self._gather('observations', 'high_value_reps', 0, B, cols, vcols)
-        goal_src = 'oracle_reps' if 'oracle_reps' in self else 'observations'  # datasets.py:348-357
-        for key, src_key, select in _hgc_outputs(out, B, goal_src, self._has_low, self.device,
-                                                 own_reps=vcols is not None):
-            out[key] = self._gather(src_key, key, select, B, cols, vcols)
-        if len(cols) > self.MAX_SAMPLE_COLS:
-            raise ValueError(f'at most {self.MAX_SAMPLE_COLS} columns per sample, got {len(cols)}')
-        idx_t = {k: torch.empty(B, dtype=torch.int64, device=self.device)
-                 for k in (_HGC_SCALARS[:4] if record else ())}
-        outs = HgcOutputs(*[_lib.ptr(idx_t.get(k)) for k in _HGC_SCALARS[:4]],
-                          *[out[k].data_ptr() for k in _HGC_SCALARS[4:]])
-        arr = (GcColumn * len(cols))(*cols)
-        return out, (arr, len(cols), B, outs), {'_' + k: t for k, t in idx_t.items()}
-
-    # sample() is GCReplayBuffer's; what differs for the hierarchical sampler:
+    # sample() is GCReplayBuffer's; what differs for the hierarchical sampler
+    # (with the hooks of _HgcHost):
     _NAME = 'HGCReplayBuffer'
     _what = 'online_hgc_sample'
-    _TRL_OK = False  # as HGCDataset
-    _VISUAL_KEYS = HGCDataset._VISUAL_KEYS
-    _CROP_KEYS = HGCDataset._CROP_KEYS
-    _visual_indices = HGCDataset._visual_indices
 
-    def _hcfg_ptr(self):
-        return ctypes.byref(self._hcfg)
-
-    def _draw_structs(self):
-        dr = HgcDraws()
-        return dr, dr.gc
-
-    def _record_struct(self, rec_t):
-        # the l_* draws exist (and are recorded) only with low_discount
-        return HgcDrawRecord(super()._record_struct(rec_t), *[_lib.ptr(rec_t.get(k)) for k in _HDRAW_LOW])
+    def _batch(self, B, record, vcols=None):
+        out, cols, outs, idx_t = self._hgc_walk(B, record, vcols)
+        if len(cols) > self.MAX_SAMPLE_COLS:
+            raise ValueError(f'at most {self.MAX_SAMPLE_COLS} columns per sample, got {len(cols)}')
+        arr = (GcColumn * len(cols))(*cols)
+        return out, (arr, len(cols), B, outs), idx_t
 
     def _sample_args(self, held, dr, rec):
         arr, ncols, B, outs = held

@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from ogbench_amd import _lib
-from ogbench_amd.datasets import Dataset, GcColumn, HGCDataset, HgcOutputs, _HGC_SCALARS
+from ogbench_amd.datasets import Dataset, GcColumn, HGCDataset
 
 dev = torch.device('cuda', 0)
 n_traj, L = 500, 2000
@@ -29,10 +29,8 @@ cfg = dict(discount=0.995, value_p_curgoal=0.2, value_p_trajgoal=0.5, value_p_ra
            actor_geom_sample=False, gc_negative=True, p_aug=0.0, frame_stack=None, subgoal_steps=100)
 h = HGCDataset(Dataset(data, device=dev), cfg, seed=0)
 B = 1024
-out, cols = h._hcolumns(B)
+out, cols, outs, _ = h._hgc_walk(B, False)
 arr = (GcColumn * len(cols))(*cols)
-ptr = lambda k: out[k].data_ptr() if k in out else None  # noqa: E731
-outs = HgcOutputs(None, None, None, None, *[ptr(k) for k in _HGC_SCALARS[4:]])
 bufs = [torch.zeros(B * 20, dtype=torch.int64, device=dev) for _ in range(2)]
 L_ = h._Lh
 stream = _lib.stream_of(dev)

@@ -388,6 +388,76 @@ def test_every_row_done_comes_back_counted(gpu):
     assert p.buf.trl_bad_samples() == total
 
 
+# ------------------------------------- the host path shared with the dataset samplers
+def _tiny_sampler(kind, gpu, seed=1):
+    """A dataset sampler of one family and mode over 3 trajectories of 10 rows."""
+    rng = np.random.RandomState(4)
+    visual, R = kind.endswith('visual'), 30
+    term = np.zeros(R, np.float32)
+    term[9::10] = 1
+    obs = rng.randint(0, 256, (R, 8, 8, 3)).astype(np.uint8) if visual else rng.normal(size=(R, 2))
+    data = dict(observations=obs, actions=rng.normal(size=(R, 2)).astype(np.float32), terminals=term, valids=1 - term)
+    cfg = dict(CFG['geom'], p_aug=0.5 if visual else None, frame_stack=3 if visual else None)
+    if not kind.startswith('gc_trl'):
+        cfg.pop('agent_name')
+    if kind.startswith('hgc'):
+        return D.HGCDataset(Dataset(data, device=gpu), dict(cfg, subgoal_steps=3), seed=seed)
+    return GCDataset(Dataset(data, device=gpu), cfg, seed=seed)
+
+
+@pytest.mark.parametrize('kind', ['gc', 'gc_visual', 'gc_trl', 'hgc', 'hgc_visual'])
+def test_dataset_samplers_name_a_wrong_length(gpu, kind):
+    s = _tiny_sampler(kind, gpu)
+    assert s._trl == (kind == 'gc_trl') and s._visual == kind.endswith('visual')
+    with pytest.raises(ValueError, match=r'idxs must have 8 entries, got 7'):
+        s.sample(8, idxs=np.arange(7))
+    with pytest.raises(ValueError, match=r"draw 'v_geom' must have 8 entries, got 9"):
+        s.sample(8, draws=dict(v_geom=np.ones(9, np.int64)))
+    out = s.sample(8, idxs=np.arange(8), record_draws=True)  # still works
+    np.testing.assert_array_equal(_np(out['_idxs']), np.arange(8))
+
+
+@pytest.mark.parametrize('kind', ['gc', 'hgc'])
+def test_unknown_draws_are_skipped_by_datasets_and_refused_by_rings(gpu, kind):
+    """The dataset samplers skip a draw they do not take (the reference's
+    fixtures hand HGCDataset an 'l_dist'); the ring buffers raise."""
+    a, b = _tiny_sampler(kind, gpu, seed=6), _tiny_sampler(kind, gpu, seed=6)
+    got = a.sample(8, draws=dict(l_dist=np.zeros(8), x_pick=np.zeros(3, np.int64)), record_draws=True)
+    exp = b.sample(8, record_draws=True)
+    assert list(got) == list(exp) and list(got['_draws']) == list(exp['_draws'])
+    for k, v in exp.items():
+        for kk, t in (v.items() if k == '_draws' else [(k, v)]):
+            assert torch.equal(got[k][kk] if k == '_draws' else got[k], t), (k, kk)
+    cls, cfg = (HGCReplayBuffer, dict(otn.CONFIGS['geom'], subgoal_steps=3)) if kind == 'hgc' else \
+        (GCReplayBuffer, dict(otn.CONFIGS['geom']))
+    cfg.pop('agent_name')
+    buf = cls.create(EX2, 3, 6, cfg, device=gpu, seed=6)
+    buf.add({k: torch.as_tensor(v).to(gpu) for k, v in _rows(np.random.RandomState(0), 3).items()},
+            torch.zeros(3, dtype=torch.bool, device=gpu))
+    with pytest.raises(ValueError, match="unknown draw 'l_dist'"):
+        buf.sample(8, draws=dict(l_dist=np.zeros(8)))
+
+
+def test_trl_layout_is_one_for_dataset_and_ring(gpu):
+    """A TRL GCDataset and a TRL GCReplayBuffer over the same snapshot return
+    the same keys, in the same order, after the data's own."""
+    cfg, rng = CFG['geom'], np.random.RandomState(2)
+    buf = GCReplayBuffer.create(EX2, 3, 6, cfg, device=gpu, seed=1)
+    for t in range(5):
+        buf.add({k: torch.as_tensor(v).to(gpu) for k, v in _rows(rng, 3).items()},
+                torch.as_tensor(np.arange(3) == t).to(gpu))
+    gc = GCDataset(Dataset(buf.snapshot()), cfg, seed=1)
+    got, exp = buf.sample(8), gc.sample(8)
+    layout = [k for k, _, _ in D._TRL_LAYOUT]
+    assert list(got)[:len(buf)] == list(buf) and list(exp)[:len(gc.dataset)] == list(gc.dataset)
+    assert list(got)[len(buf):] == list(exp)[len(gc.dataset):] == layout
+    assert sorted(layout[:4]) == sorted(GCReplayBuffer.RESERVED[:4]) and layout[4:] == list(GCReplayBuffer._TRL_KEYS)
+    for k in layout:
+        assert got[k].dtype == exp[k].dtype and torch.equal(got[k], exp[k]), k
+    _assert_aliases(got)
+    _assert_aliases(exp)
+
+
 # ---------------------------------------------------------------- add_step end to end
 def test_add_step_on_a_real_auto_reset_env(gpu):
     n, T, steps = 64, 8, 20
