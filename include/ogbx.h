@@ -306,7 +306,12 @@ ogbx_status ogbx_maze_set_goal(ogbx_maze_t env, const int32_t* goal_ij, const ui
  *  GCDataset.sample :213-294, GCDataset.sample_goals :296-327)
  * ====================================================================== */
 
-/* One dataset column to gather into the batch. */
+/* One dataset column to gather into the batch.  Any row_bytes > 0, any
+ * alignment of src and dst and any src_stride >= row_bytes (or 0) is
+ * accepted: rows are copied in the widest unit W of {16, 8, 4, 1} bytes with
+ * row_bytes % W == 0 and (src | dst | src_stride) % W == 0, so no access is
+ * wider than the descriptor's own alignment and nothing is written outside
+ * dst's rows (tests/test_gather_gpu.py). */
 typedef struct {
   const void* src;   /* device, [num_rows, row_bytes] contiguous */
   void* dst;         /* device, [num_batches * batch, row_bytes] */
