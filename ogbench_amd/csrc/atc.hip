@@ -211,11 +211,8 @@ ogbx_status ogbx_atc_sample(const ogbx_gc_buffer* buf, const ogbx_atc_column* co
 
   int dev = 0;
   OGBX_HIP(hipGetDevice(&dev));
-  bool ok = on_device(buf->traj_end, dev) && on_device(col->src, dev) && on_device(col->anchor, dev) &&
-            on_device(col->positive, dev);
-  for (const int64_t* q : {valid, idxs, pick, crop_from, (const int64_t*)o.idxs, (const int64_t*)o.pick,
-                           (const int64_t*)o.crop_from, (const int64_t*)o.bad_count})
-    ok = ok && (!q || on_device(q, dev));
+  const bool ok = all_on_device(dev, {buf->traj_end, col->src, col->anchor, col->positive, valid, idxs, pick, crop_from,
+                                      o.idxs, o.pick, o.crop_from, o.bad_count});
   OGBX_CHECK(ok, OGBX_EINVAL, who + "every pointer must be device memory of the current device");
 
   a.traj_end = buf->traj_end;

@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/ogbx.h"
@@ -29,6 +30,30 @@ ogbx_status use_device(int32_t device);
   do {                                           \
     if (!(cond)) return ::ogbx::fail(code, msg); \
   } while (0)
+
+// Pass a failed check of a helper on to the caller.
+#define GC_TRY(expr)                       \
+  do {                                     \
+    if (ogbx_status _st = (expr)) return _st; \
+  } while (0)
+
+// Device memory of `device`?
+inline bool on_device(const void* ptr, int device) {
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return attr.type == hipMemoryTypeDevice && attr.device == device;
+}
+
+// Every pointer of the list is; a null entry is an absent optional pointer, so
+// a required pointer must have been refused for null before it comes here.
+inline bool all_on_device(int device, std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (p && !on_device(p, device)) return false;
+  return true;
+}
 
 // Launch-error check after a kernel launch (hipGetLastError is cheap and
 // capture-safe).
@@ -112,6 +137,9 @@ __host__ __device__ inline float u01f_from(uint32_t w) { return (float)(w >> 8) 
 __host__ __device__ inline uint32_t bounded_u32(uint32_t w, uint32_t n) {
   return (uint32_t)(((uint64_t)w * (uint64_t)n) >> 32);
 }
+
+// Row r moved into [0, R): whatever an injected index holds.
+__device__ inline int64_t clamp_row(int64_t r, int64_t R) { return r < 0 ? 0 : (r >= R ? R - 1 : r); }
 
 enum StreamTag : uint32_t {
   kTagMazeReset = 0x4D5A0001u,

@@ -247,20 +247,11 @@ ogbx_status fs_disjoint(const std::string& who, std::initializer_list<FsRange> o
   return OGBX_OK;
 }
 
-bool fs_on_device(const void* ptr, int device) {
-  hipPointerAttribute_t attr{};
-  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return attr.type == hipMemoryTypeDevice && attr.device == device;
-}
-
 ogbx_status fs_device(const std::string& who, std::initializer_list<FsRange> ptrs) {
   int dev = 0;
   OGBX_HIP(hipGetDevice(&dev));
   for (const FsRange& r : ptrs)
-    OGBX_CHECK(!r.p || fs_on_device(r.p, dev), OGBX_EINVAL,
+    OGBX_CHECK(!r.p || on_device(r.p, dev), OGBX_EINVAL,
                who + r.name + " is not memory of the current device");
   return OGBX_OK;
 }

@@ -2,10 +2,15 @@
 // share: the per-sample draw chain (index loads, goal relabel), the tile
 // helpers (Philox words, XCD-major numbering, row copies) and the host-side
 // argument checks and launch parameters of the ogbx_gc_* / ogbx_hgc_* /
-// ogbx_trl_* entry points.  The samplers of replay.hip, online.hip and
-// online_hgc.hip take the tile helpers, the goal draws and their record
-// (goal_side_draws, store_draw_record) and the gather-column check
-// (check_gather_columns) from here too.  Internal to libogbx.
+// ogbx_trl_* entry points.  The samplers of replay.hip, online.hip,
+// online_hgc.hip and online_trl.hip take the tile helpers, the goal draws and
+// their record (goal_side_draws, store_draw_record) and the gather-column check
+// (check_gather_columns) from here too, and with them the first wave's
+// prologue (sample_words, root_picks), store_gc_scalars,
+// sample_grid and the hierarchical host checks (check_hgc_config,
+// check_hgc_outputs).  trl_device.h holds what the two TRL kernels share beyond
+// that; on_device / all_on_device and clamp_row are common.h's.  Internal to
+// libogbx.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,7 +22,6 @@
 #include "common.h"
 
 namespace ogbx {
-
 
 constexpr int kGcMaxTile = 64;
 constexpr int kGcMaxCols = 32;
@@ -317,6 +321,59 @@ __device__ inline u32x4 tile_word(const uint4 (*wb)[kGcMaxTile], int q, int b) {
   return u32x4{v.x, v.y, v.z, v.w};
 }
 
+// ------- the first wave's prologue, over a dataset and over the ring; a kernel takes
+// a helper only where its gfx950 code stays (profiles/sampler_device_refactor_isa.txt)
+// Philox words 0 .. 4 of sample s, the lane's sample b of the tile: the tile's
+// words from LDS (tile_philox), else (kInLane) computed in the lane.
+template <bool kInLane>
+__device__ __forceinline__ void sample_words(const uint4 (*wb)[kGcMaxTile], int b, int64_t s, uint32_t call_lo,
+                                             uint32_t call_hi, uint32_t k0, uint32_t k1, u32x4* w) {
+  const uint64_t su = (uint64_t)s;
+  const uint32_t c0 = (uint32_t)su, c3 = (uint32_t)(su >> 32) ^ call_hi;
+  if constexpr (kInLane) {
+    w[0] = philox4x32_10({c0, call_lo, 0u, c3}, k0, k1);
+    w[1] = philox4x32_10({c0, call_lo, 1u, c3}, k0, k1);
+    w[2] = philox4x32_10({c0, call_lo, 2u, c3}, k0, k1);
+    w[3] = philox4x32_10({c0, call_lo, 3u, c3}, k0, k1);
+    w[4] = philox4x32_10({c0, call_lo, 4u, c3}, k0, k1);
+  } else {
+    w[0] = tile_word(wb, 0, b), w[1] = tile_word(wb, 1, b), w[2] = tile_word(wb, 2, b), w[3] = tile_word(wb, 3, b),
+    w[4] = tile_word(wb, 4, b);
+  }
+}
+
+// The picks of the sample, its value goal and its actor goal out of npick
+// (words w0.xy, w0.zw, w1.xy), an injected pick in place of its Philox value;
+// kClamp (the ring) moves injected picks into [0, npick).  *pick stays -1 where
+// the call gave the row itself (dr.idxs).
+template <bool kInj, bool kClamp>
+__device__ __forceinline__ void root_picks(const ogbx_gc_draws& dr, int64_t s, const u32x4& w0, const u32x4& w1,
+                                           int64_t npick, int64_t nrows, int64_t* idx, int64_t* pick,
+                                           int64_t* v_pick, int64_t* a_pick) {
+  auto given = [s](const int64_t* p, int64_t n) { return kClamp ? clamp_row(p[s], n) : p[s]; };
+  *pick = -1;
+  if (kInj && dr.idxs) {
+    *idx = given(dr.idxs, nrows);
+  } else {
+    *pick = (kInj && dr.pick) ? given(dr.pick, npick) : (int64_t)bounded64(w0.x, w0.y, (uint64_t)npick);
+    if (kClamp) *idx = *pick;  // over the ring the pick is the row (a pick table maps it next)
+  }
+  *v_pick = (kInj && dr.v_pick) ? given(dr.v_pick, npick) : (int64_t)bounded64(w0.z, w0.w, (uint64_t)npick);
+  *a_pick = (kInj && dr.a_pick) ? given(dr.a_pick, npick) : (int64_t)bounded64(w1.x, w1.y, (uint64_t)npick);
+}
+
+// The per-sample scalars of a GC batch (the index outputs may be NULL).
+__device__ __forceinline__ void store_gc_scalars(int64_t* idxs_out, int64_t* vgoal_out, int64_t* agoal_out,
+                                                 double* masks, double* rewards, int gc_negative, int64_t s,
+                                                 int64_t idx, int64_t vg, int64_t ag) {
+  if (idxs_out) idxs_out[s] = idx;
+  if (vgoal_out) vgoal_out[s] = vg;
+  if (agoal_out) agoal_out[s] = ag;
+  const double succ = idx == vg ? 1.0 : 0.0;
+  masks[s] = 1.0 - succ;
+  rewards[s] = succ - (gc_negative ? 1.0 : 0.0);
+}
+
 // ---------------------------------------------------------------- host side
 // Every column 4-byte granular and aligned with rows of <= 128 words (the
 // per-wave job copy of copy_tile).
@@ -350,11 +407,6 @@ static bool periodic_ok(const ogbx_gc_buffer& b) {
 // ------------------------------------------------------------ argument checks
 // Every check of the GC / HGC entry points lives here, once; an entry point
 // runs its checks before its first HIP call.  `who` is the entry point's name.
-#define GC_TRY(expr)                       \
-  do {                                     \
-    if (ogbx_status _st = (expr)) return _st; \
-  } while (0)
-
 static std::string named(const char* who, const char* what) { return std::string(who) + ": " + what; }
 
 static ogbx_status check_buffer(const ogbx_gc_buffer* buf) {
@@ -393,6 +445,29 @@ static ogbx_status check_gather_columns(const ogbx_gc_column* cols, int32_t num_
   return OGBX_OK;
 }
 
+// The hierarchical checks ogbx_hgc_* and ogbx_online_hgc_sample share.  The
+// bound on the subgoal steps and its wording are the entry point's: >= 0 and
+// "negative subgoal steps" over a dataset, >= 1 over the ring.
+static ogbx_status check_hgc_config(const ogbx_hgc_config* hcfg, const char* who, int64_t min_steps,
+                                    const char* steps_words) {
+  OGBX_CHECK(hcfg->hv_mask_table && hcfg->hv_reward_table && hcfg->lv_mask_table && hcfg->lv_reward_table,
+             OGBX_EINVAL, named(who, "missing reward/mask tables"));
+  OGBX_CHECK(hcfg->value_subgoal_steps >= min_steps && hcfg->low_subgoal_steps >= min_steps &&
+                 hcfg->actor_subgoal_steps >= min_steps,
+             OGBX_EINVAL, named(who, steps_words));
+  OGBX_CHECK(!hcfg->has_low_value_goals || (hcfg->low_discount > 0.0 && hcfg->low_discount < 1.0), OGBX_EINVAL,
+             named(who, "low_discount must be in (0, 1)"));
+  return OGBX_OK;
+}
+
+static ogbx_status check_hgc_outputs(const ogbx_hgc_outputs* out, const char* who) {
+  OGBX_CHECK(out && out->high_value_offsets && out->high_value_subgoal_steps && out->high_value_masks &&
+                 out->high_value_rewards && out->low_value_subgoal_steps && out->low_value_masks &&
+                 out->low_value_rewards && out->masks && out->rewards,
+             OGBX_EINVAL, named(who, "missing scalar output"));
+  return OGBX_OK;
+}
+
 // Bits 0 .. max_select: the select codes of the dataset samplers.
 constexpr uint32_t selects_up_to(int max_select) { return (2u << max_select) - 1u; }
 
@@ -410,6 +485,14 @@ static ogbx_status check_columns(const ogbx_gc_column* cols, int32_t num_cols, i
 // workgroups of 256 threads; measured against 2 and 4 samples per workgroup
 // and 64- to 1024-thread workgroups), then up to 64 per workgroup
 static int64_t gc_tile(int64_t total) { return std::clamp<int64_t>(total / 1024, 1, kGcMaxTile); }
+
+// Samples per workgroup and workgroups of a launch; false when the grid passes
+// the launch limit (the ring and replay entry points refuse that).
+static bool sample_grid(int64_t total, int64_t* tile, int64_t* blocks) {
+  *tile = gc_tile(total);
+  *blocks = (total + *tile - 1) / *tile;
+  return *blocks <= 0x7fffffffll;
+}
 
 // What a (seed, config) fixes for every call: the Philox key and the
 // log(1 - p) terms of the geometric draws (p = 1 - discount).

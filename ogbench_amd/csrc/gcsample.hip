@@ -26,8 +26,9 @@
 
 namespace ogbx {
 
-// The draw chain, the tile helpers and the shared argument checks: gc_device.h
-// (trl.hip builds its kernel from the same pieces).
+// The draw chain, the first wave's prologue, the tile helpers and the shared
+// argument checks: gc_device.h (trl.hip and the ring samplers build their
+// kernels from the same pieces).
 
 template <bool kInj>
 __global__ void __launch_bounds__(256) gc_sample_kernel(
@@ -38,7 +39,7 @@ __global__ void __launch_bounds__(256) gc_sample_kernel(
   __shared__ int64_t sel[4][kGcMaxTile];
   __shared__ uint4 wb[(!kInj && kGcSpread) ? 5 : 1][kGcMaxTile];
   const int64_t base = xcd_tile() * tile;
-  int n_here = (int)((total - base) < tile ? (total - base) : tile);
+  const int n_here = (int)((total - base) < tile ? (total - base) : tile);
   if (!kInj && kGcSpread) {
     tile_philox(wb, 5, n_here, base, call_lo, call_hi, k0, k1);
     __syncthreads();
@@ -50,49 +51,30 @@ __global__ void __launch_bounds__(256) gc_sample_kernel(
     const int b = (int)threadIdx.x % n_here;
     const bool own = (int)threadIdx.x < n_here;
     const int64_t s = base + b;
-    const uint64_t su = (uint64_t)s;
-    const uint32_t c0 = (uint32_t)su, c3 = (uint32_t)(su >> 32) ^ call_hi;
-    u32x4 w0, w1, w2, w3, w4;
-    if (!kInj && kGcSpread) {
-      w0 = tile_word(wb, 0, b), w1 = tile_word(wb, 1, b), w2 = tile_word(wb, 2, b), w3 = tile_word(wb, 3, b),
-      w4 = tile_word(wb, 4, b);
-    } else {
-      w0 = philox4x32_10({c0, call_lo, 0u, c3}, k0, k1);
-      w1 = philox4x32_10({c0, call_lo, 1u, c3}, k0, k1);
-      w2 = philox4x32_10({c0, call_lo, 2u, c3}, k0, k1);
-      w3 = philox4x32_10({c0, call_lo, 3u, c3}, k0, k1);
-      w4 = philox4x32_10({c0, call_lo, 4u, c3}, k0, k1);
-    }
+    u32x4 w[5];
+    sample_words<kInj || !kGcSpread>(wb, b, s, call_lo, call_hi, k0, k1, w);
     const int64_t npick = buf.valid_idxs ? buf.num_valid : buf.num_rows;
     // sample index (datasets.py:65-70)
-    int64_t idx = 0, pick = -1, final_idx;
-    if (kInj && dr.idxs) idx = dr.idxs[s];
-    else pick = (kInj && dr.pick) ? dr.pick[s] : (int64_t)bounded64(w0.x, w0.y, (uint64_t)npick);
+    int64_t idx = 0, pick, final_idx;
     GoalDraws v, a;
-    v.pick = (kInj && dr.v_pick) ? dr.v_pick[s] : (int64_t)bounded64(w0.z, w0.w, (uint64_t)npick);
-    a.pick = (kInj && dr.a_pick) ? dr.a_pick[s] : (int64_t)bounded64(w1.x, w1.y, (uint64_t)npick);
+    root_picks<kInj, false>(dr, s, w[0], w[1], npick, buf.num_rows, &idx, &pick, &v.pick, &a.pick);
     index_loads(buf, kInj && dr.idxs != nullptr, pick, &idx, &final_idx);
     const int64_t v_rand = cfg.value_cur_is_one ? 0 : rand_goal_of(buf, v.pick);
     const int64_t a_rand = cfg.actor_cur_is_one ? 0 : rand_goal_of(buf, a.pick);
     const int64_t next = idx + 1 < buf.num_rows ? idx + 1 : buf.num_rows - 1;
-    goal_side_draws<kInj>(dr, cfg, s, w1, w2, w3, w4, v_log_q, a_log_q, v, a);
+    goal_side_draws<kInj>(dr, cfg, s, w[1], w[2], w[3], w[4], v_log_q, a_log_q, v, a);
     const int64_t vg = sample_goal(idx, final_idx, v, v_rand, cfg.value_p_curgoal,
                                    cfg.value_traj_thresh, cfg.value_geom_sample, cfg.value_cur_is_one);
     const int64_t ag = sample_goal(idx, final_idx, a, a_rand, cfg.actor_p_curgoal,
                                    cfg.actor_traj_thresh, cfg.actor_geom_sample, cfg.actor_cur_is_one);
     if (own) {
-    sel[0][b] = idx;
-    sel[1][b] = next;
-    sel[2][b] = vg;
-    sel[3][b] = ag;
-    if (idxs_out) idxs_out[s] = idx;
-    if (vgoal_out) vgoal_out[s] = vg;
-    if (agoal_out) agoal_out[s] = ag;
-    const double succ = idx == vg ? 1.0 : 0.0;
-    masks[s] = 1.0 - succ;
-    rewards[s] = succ - (cfg.gc_negative ? 1.0 : 0.0);
-    store_draw_record(rec, s, pick, v, a);
-    }  // own
+      sel[0][b] = idx;
+      sel[1][b] = next;
+      sel[2][b] = vg;
+      sel[3][b] = ag;
+      store_gc_scalars(idxs_out, vgoal_out, agoal_out, masks, rewards, cfg.gc_negative, s, idx, vg, ag);
+      store_draw_record(rec, s, pick, v, a);
+    }
   }
   __syncthreads();
   copy_tile<0>(cols, num_cols, sel, base, n_here, flat4);
@@ -269,12 +251,9 @@ __global__ void __launch_bounds__(256) hgc_sample_kernel(
     }
     const int64_t npick = buf.valid_idxs ? buf.num_valid : buf.num_rows;
     const ogbx_gc_draws& g = dr.gc;
-    int64_t idx = 0, pick = -1, fin;
-    if (kInj && g.idxs) idx = g.idxs[s];
-    else pick = (kInj && g.pick) ? g.pick[s] : (int64_t)bounded64(w0.x, w0.y, (uint64_t)npick);
+    int64_t idx = 0, pick, fin;
     GoalDraws v, a, l;
-    v.pick = (kInj && g.v_pick) ? g.v_pick[s] : (int64_t)bounded64(w0.z, w0.w, (uint64_t)npick);
-    a.pick = (kInj && g.a_pick) ? g.a_pick[s] : (int64_t)bounded64(w1.x, w1.y, (uint64_t)npick);
+    root_picks<kInj, false>(g, s, w0, w1, npick, buf.num_rows, &idx, &pick, &v.pick, &a.pick);
     u32x4 w5{}, w6{};
     int64_t l_rand = 0;
     if (hc.has_low_value_goals) {
@@ -631,24 +610,6 @@ static ogbx_status check_ahead(int64_t total, const int64_t* ahead_in, const int
   return OGBX_OK;
 }
 
-static ogbx_status check_hgc_config(const ogbx_hgc_config* hcfg, const char* who) {
-  OGBX_CHECK(hcfg->hv_mask_table && hcfg->hv_reward_table && hcfg->lv_mask_table && hcfg->lv_reward_table,
-             OGBX_EINVAL, named(who, "missing reward/mask tables"));
-  OGBX_CHECK(hcfg->value_subgoal_steps >= 0 && hcfg->low_subgoal_steps >= 0 && hcfg->actor_subgoal_steps >= 0,
-             OGBX_EINVAL, named(who, "negative subgoal steps"));
-  OGBX_CHECK(!hcfg->has_low_value_goals || (hcfg->low_discount > 0.0 && hcfg->low_discount < 1.0), OGBX_EINVAL,
-             named(who, "low_discount must be in (0, 1)"));
-  return OGBX_OK;
-}
-
-static ogbx_status check_hgc_outputs(const ogbx_hgc_outputs* out, const char* who) {
-  OGBX_CHECK(out && out->high_value_offsets && out->high_value_subgoal_steps && out->high_value_masks &&
-                 out->high_value_rewards && out->low_value_subgoal_steps && out->low_value_masks &&
-                 out->low_value_rewards && out->masks && out->rewards,
-             OGBX_EINVAL, named(who, "missing scalar output"));
-  return OGBX_OK;
-}
-
 // GC per-sample scalar outputs (the index outputs may be NULL).
 struct GcScalars {
   int64_t *idxs = nullptr, *vg = nullptr, *ag = nullptr;
@@ -662,7 +623,8 @@ static ogbx_status launch_gc_sample(const ogbx_gc_buffer& buf, const ogbx_gc_con
                                     const GcColumns& cc, int32_t num_cols, bool flat4, int64_t total,
                                     uint64_t call, const ogbx_gc_draws& dr, const ogbx_gc_draw_record& rec,
                                     const GcScalars& o, hipStream_t s) {
-  const int64_t tile = gc_tile(total), blocks = (total + tile - 1) / tile;
+  int64_t tile, blocks;
+  sample_grid(total, &tile, &blocks);
   const auto kern = any_draw(dr) ? gc_sample_kernel<true> : gc_sample_kernel<false>;
   hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, s, buf, cfg, cc, num_cols, total, (int)tile, dr,
                      pr.k0, pr.k1, (uint32_t)call, (uint32_t)(call >> 32), pr.v_log_q, pr.a_log_q, o.idxs, o.vg,
@@ -676,7 +638,8 @@ static ogbx_status launch_hgc_sample(const ogbx_gc_buffer& buf, const ogbx_gc_co
                                      int32_t num_cols, bool flat4, int64_t total, uint64_t call,
                                      const ogbx_hgc_draws& dr, const ogbx_hgc_draw_record& rec,
                                      const ogbx_hgc_outputs& o, hipStream_t s) {
-  const int64_t tile = gc_tile(total), blocks = (total + tile - 1) / tile;
+  int64_t tile, blocks;
+  sample_grid(total, &tile, &blocks);
   const bool inj = any_draw(dr.gc) || dr.l_pick || dr.l_geom || dr.l_u_traj || dr.l_u_cur;
   const auto kern = inj ? hgc_sample_kernel<true> : hgc_sample_kernel<false>;
   hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, s, buf, cfg, hcfg, cc, num_cols, total, (int)tile,
@@ -766,7 +729,7 @@ ogbx_status ogbx_hgc_sample(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg
   GcColumns cc{};
   bool flat4;
   GC_TRY(check_hgc_outputs(out, who));
-  GC_TRY(check_hgc_config(hcfg, who));
+  GC_TRY(check_hgc_config(hcfg, who, 0, "negative subgoal steps"));
   GC_TRY(check_columns(cols, num_cols, batch, num_batches, kHgcSel - 1, who, &cc, &flat4));
   GC_TRY(check_buffer(buf));
   return launch_hgc_sample(*buf, *cfg, *hcfg, gc_params(seed, *cfg, hcfg), cc, num_cols,
@@ -785,7 +748,7 @@ ogbx_status ogbx_hgc_sample_ahead(const ogbx_gc_buffer* buf, const ogbx_gc_confi
   GcColumns cc{};
   bool flat4;
   GC_TRY(check_hgc_outputs(out, who));
-  GC_TRY(check_hgc_config(hcfg, who));
+  GC_TRY(check_hgc_config(hcfg, who, 0, "negative subgoal steps"));
   GC_TRY(check_columns(cols, num_cols, batch, num_batches, kHgcSel - 1, who, &cc, &flat4));
   GC_TRY(check_ahead(batch * num_batches, ahead_in, ahead_out, who));
   GC_TRY(check_buffer(buf));
@@ -854,7 +817,7 @@ ogbx_status ogbx_gc_plan_create(const ogbx_gc_buffer* buf, const ogbx_gc_config*
   const char* who = "ogbx_gc_plan_create";
   OGBX_CHECK(buf && cfg && plan, OGBX_EINVAL, named(who, "null argument"));
   GC_TRY(check_buffer(buf));
-  if (hcfg) GC_TRY(check_hgc_config(hcfg, who));
+  if (hcfg) GC_TRY(check_hgc_config(hcfg, who, 0, "negative subgoal steps"));
   auto* p = new (std::nothrow) ogbx_gc_plan_s();
   OGBX_CHECK(p, OGBX_ENOMEM, "ogbx_gc_plan_create: out of host memory");
   p->buf = *buf;

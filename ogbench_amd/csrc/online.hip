@@ -22,8 +22,8 @@
 // on flat indices by sample_goal, and each selector is mapped to its physical
 // row.  The ring's view, the row map and the end lookup live in
 // online_device.h, shared with online_hgc_sample_kernel (online_hgc.hip); the
-// goal draws besides the picks, the draw record and the host's column check
-// are gc_device.h's (goal_side_draws, store_draw_record, check_gather_columns).
+// prologue, the picks, the goal draws, the scalar stores, the draw record, the
+// column check and the launch grid are gc_device.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,7 +33,6 @@
 #include "gc_device.h"
 #include "online_device.h"
 #include "replay_device.h"
-#include "visual_tile.h"
 
 namespace ogbx {
 
@@ -89,40 +88,24 @@ __global__ void __launch_bounds__(256) online_gc_sample_kernel(
     tile_philox(wb, 5, n_here, base, call_lo, call_hi, k0, k1);
     __syncthreads();
   }
-  // the whole first wave runs the sample chains (lane b % n_here; lanes
-  // b < n_here store): see gc_sample_kernel
-  if (threadIdx.x < 64 && n_here > 0) {
+  if (threadIdx.x < 64 && n_here > 0) {  // the whole first wave: see gc_sample_kernel
     const int b = (int)threadIdx.x % n_here;
     const bool own = (int)threadIdx.x < n_here;
     const int64_t s = base + b;
-    const uint64_t su = (uint64_t)s;
-    const uint32_t c0 = (uint32_t)su, c3 = (uint32_t)(su >> 32) ^ call_hi;
-    u32x4 w0, w1, w2, w3, w4;
-    if (!kInj && kGcSpread) {
-      w0 = tile_word(wb, 0, b), w1 = tile_word(wb, 1, b), w2 = tile_word(wb, 2, b), w3 = tile_word(wb, 3, b),
-      w4 = tile_word(wb, 4, b);
-    } else {
-      w0 = philox4x32_10({c0, call_lo, 0u, c3}, k0, k1);
-      w1 = philox4x32_10({c0, call_lo, 1u, c3}, k0, k1);
-      w2 = philox4x32_10({c0, call_lo, 2u, c3}, k0, k1);
-      w3 = philox4x32_10({c0, call_lo, 3u, c3}, k0, k1);
-      w4 = philox4x32_10({c0, call_lo, 4u, c3}, k0, k1);
-    }
+    u32x4 w[5];
+    sample_words<kInj || !kGcSpread>(wb, b, s, call_lo, call_hi, k0, k1, w);
     const int64_t npick = ring.npick;
     // the slot layout of gc_sample_kernel over npick rows without valid_idxs;
     // injected values are clamped into [0, npick)
-    int64_t idx, pick = -1;
-    if (kInj && dr.idxs) idx = clamp_row(dr.idxs[s], npick);
-    else idx = pick = (kInj && dr.pick) ? clamp_row(dr.pick[s], npick) : (int64_t)bounded64(w0.x, w0.y, (uint64_t)npick);
+    int64_t idx, pick;
     GoalDraws v, a;
-    v.pick = (kInj && dr.v_pick) ? clamp_row(dr.v_pick[s], npick) : (int64_t)bounded64(w0.z, w0.w, (uint64_t)npick);
-    a.pick = (kInj && dr.a_pick) ? clamp_row(dr.a_pick[s], npick) : (int64_t)bounded64(w1.x, w1.y, (uint64_t)npick);
+    root_picks<kInj, true>(dr, s, w[0], w[1], npick, npick, &idx, &pick, &v.pick, &a.pick);
     // the row's episode end (online_device.h): ep_seq / cur_seq, then ep_end
     int64_t e, k;
     split_flat(ring, idx, &e, &k);
     const int64_t prow = phys_row(ring, e, k);
     const int64_t final_idx = episode_end_flat(ring, episode_seq(ring, e, prow), idx, e, k);
-    goal_side_draws<kInj>(dr, cfg, s, w1, w2, w3, w4, v_log_q, a_log_q, v, a);
+    goal_side_draws<kInj>(dr, cfg, s, w[1], w[2], w[3], w[4], v_log_q, a_log_q, v, a);
     int64_t vg = sample_goal(idx, final_idx, v, v.pick, cfg.value_p_curgoal, cfg.value_traj_thresh,
                              cfg.value_geom_sample, cfg.value_cur_is_one);
     int64_t ag = sample_goal(idx, final_idx, a, a.pick, cfg.actor_p_curgoal, cfg.actor_traj_thresh,
@@ -136,12 +119,7 @@ __global__ void __launch_bounds__(256) online_gc_sample_kernel(
       sel[1][b] = prow;
       sel[2][b] = vrow;
       sel[3][b] = arow;
-      if (idxs_out) idxs_out[s] = idx;
-      if (vgoal_out) vgoal_out[s] = vg;
-      if (agoal_out) agoal_out[s] = ag;
-      const double succ = idx == vg ? 1.0 : 0.0;
-      masks[s] = 1.0 - succ;
-      rewards[s] = succ - (cfg.gc_negative ? 1.0 : 0.0);
+      store_gc_scalars(idxs_out, vgoal_out, agoal_out, masks, rewards, cfg.gc_negative, s, idx, vg, ag);
       store_draw_record(rec, s, pick, v, a);
     }
   }
@@ -220,9 +198,8 @@ ogbx_status ogbx_online_gc_sample(const ogbx_online_ring* ring, const ogbx_gc_co
   // the row itself and the two goals: a ring stores its own next_observations
   GC_TRY(check_gather_columns<true>(batch->cols, num_cols, 0b1101u, "ogbx_online_gc_sample", &cc, &flat4));
   const int64_t total = batch->total;
-  const int64_t tile = gc_tile(total);
-  const int64_t blocks = (total + tile - 1) / tile;
-  OGBX_CHECK(blocks <= 0x7fffffffll, OGBX_EINVAL, who + "too many samples for one launch");
+  int64_t tile, blocks;
+  OGBX_CHECK(sample_grid(total, &tile, &blocks), OGBX_EINVAL, who + "too many samples for one launch");
 
   const OnlineView v = online_view(*ring);
   const ogbx_gc_draws dr = draws ? *draws : ogbx_gc_draws{};

@@ -11,9 +11,10 @@
 // online_hgc_sample_kernel: hgc_sample_kernel's tile structure, slot layout and
 // ten selectors (gcsample.hip, gc_device.h, gc_select.h) with the index loads
 // replaced by the ring's (online_device.h), as online_gc_sample_kernel does it
-// for the two GC goals, with the same pieces of gc_device.h (goal_side_draws,
-// store_draw_record, check_gather_columns); the l_* draws and their record are
-// written here.  All goal and subgoal arithmetic runs on flat indices;
+// for the two GC goals, with the same pieces of gc_device.h and the host
+// checks of ogbx_hgc_sample; the picks, words 5 and 6, the l_* draws and their
+// record are written here (profiles/sampler_device_refactor_isa.txt).  All
+// goal and subgoal arithmetic runs on flat indices;
 // the five derived selectors stay in [idx, fin], i.e. in the sample's env, so
 // their physical rows need no second division.
 #include <hip/hip_runtime.h>
@@ -25,7 +26,6 @@
 #include "gc_device.h"
 #include "gc_select.h"
 #include "online_device.h"
-#include "visual_tile.h"
 
 namespace ogbx {
 
@@ -77,27 +77,29 @@ __global__ void __launch_bounds__(256) online_hgc_sample_kernel(
     const int b = (int)threadIdx.x % n_here;
     const bool own = (int)threadIdx.x < n_here;
     const int64_t s = base + b;
-    const u32x4 w0 = tile_word(wb, 0, b), w1 = tile_word(wb, 1, b), w2 = tile_word(wb, 2, b),
-                w3 = tile_word(wb, 3, b), w4 = tile_word(wb, 4, b);
-    u32x4 w5{}, w6{};
+    u32x4 w[5];
+    sample_words<false>(wb, b, s, call_lo, call_hi, k0, k1, w);
+    u32x4 w5{}, w6{};  // read here, not by sample_words: through it the two came out in other registers
     if (hc.has_low_value_goals) w5 = tile_word(wb, 5, b), w6 = tile_word(wb, 6, b);
     const int64_t npick = ring.npick;
     const ogbx_gc_draws& g = dr.gc;
     // the slot layout of hgc_sample_kernel over npick rows without valid_idxs;
     // injected values are clamped into [0, npick)
+    // written out, not root_picks: it moves this kernel (profiles/sampler_device_refactor_isa.txt)
     int64_t idx, pick = -1;
     if (kInj && g.idxs) idx = clamp_row(g.idxs[s], npick);
-    else idx = pick = (kInj && g.pick) ? clamp_row(g.pick[s], npick) : (int64_t)bounded64(w0.x, w0.y, (uint64_t)npick);
+    else
+      idx = pick = (kInj && g.pick) ? clamp_row(g.pick[s], npick) : (int64_t)bounded64(w[0].x, w[0].y, (uint64_t)npick);
+    GoalDraws v, a, l{};
     // the row's episode (online_device.h): ep_seq / cur_seq are in flight
     // while the draws below, which do not depend on them, are computed
     int64_t e, k;
     split_flat(ring, idx, &e, &k);
     const int64_t prow = phys_row(ring, e, k);
     const EpisodeSeq eps = episode_seq(ring, e, prow);
-    GoalDraws v, a, l{};
-    v.pick = (kInj && g.v_pick) ? clamp_row(g.v_pick[s], npick) : (int64_t)bounded64(w0.z, w0.w, (uint64_t)npick);
-    a.pick = (kInj && g.a_pick) ? clamp_row(g.a_pick[s], npick) : (int64_t)bounded64(w1.x, w1.y, (uint64_t)npick);
-    goal_side_draws<kInj>(g, cfg, s, w1, w2, w3, w4, v_log_q, a_log_q, v, a);
+    v.pick = (kInj && g.v_pick) ? clamp_row(g.v_pick[s], npick) : (int64_t)bounded64(w[0].z, w[0].w, (uint64_t)npick);
+    a.pick = (kInj && g.a_pick) ? clamp_row(g.a_pick[s], npick) : (int64_t)bounded64(w[1].x, w[1].y, (uint64_t)npick);
+    goal_side_draws<kInj>(g, cfg, s, w[1], w[2], w[3], w[4], v_log_q, a_log_q, v, a);
     if (hc.has_low_value_goals) {
       l.pick = (kInj && dr.l_pick) ? clamp_row(dr.l_pick[s], npick) : (int64_t)bounded64(w5.x, w5.y, (uint64_t)npick);
       l.geom = (kInj && dr.l_geom) ? dr.l_geom[s] : geometric_from(u01_from(w5.z, w5.w), l_log_q);
@@ -177,11 +179,11 @@ __global__ void __launch_bounds__(256) online_hgc_sample_kernel(
 template <class Cols>
 static ogbx_status launch_online_hgc(const OnlineView& v, const ogbx_gc_config& cfg, const ogbx_hgc_config& hcfg,
                                      const GcParams& pr, const ogbx_gc_column* cols, int32_t num_cols, bool flat4,
-                                     int64_t total, uint64_t call, const ogbx_hgc_draws& dr,
-                                     const ogbx_hgc_draw_record& rec, const ogbx_hgc_outputs& o, hipStream_t s) {
+                                     int64_t total, int64_t tile, int64_t blocks, uint64_t call,
+                                     const ogbx_hgc_draws& dr, const ogbx_hgc_draw_record& rec,
+                                     const ogbx_hgc_outputs& o, hipStream_t s) {
   Cols cc{};
   for (int i = 0; i < num_cols; ++i) cc.c[i] = cols[i];
-  const int64_t tile = gc_tile(total), blocks = (total + tile - 1) / tile;
   // injected draws or a draw record: the Philox-only instance carries neither
   const bool inj = any_draw(dr.gc) || dr.l_pick || dr.l_geom || dr.l_u_traj || dr.l_u_cur || rec.gc.pick || rec.l_pick;
   const auto kern = inj ? online_hgc_sample_kernel<true, Cols> : online_hgc_sample_kernel<false, Cols>;
@@ -205,29 +207,22 @@ ogbx_status ogbx_online_hgc_sample(const ogbx_online_ring* ring, const ogbx_gc_c
                                    int64_t total, const ogbx_hgc_draws* draws, const ogbx_hgc_outputs* out,
                                    const ogbx_hgc_draw_record* record, uint64_t seed, uint64_t call_index,
                                    void* stream) {
-  const std::string who = "ogbx_online_hgc_sample: ";
+  const char* name = "ogbx_online_hgc_sample";
+  const std::string who = std::string(name) + ": ";
   if (ogbx_status st = check_ring(ring, who)) return st;
   OGBX_CHECK(cfg && hcfg && out, OGBX_EINVAL, who + "null argument");
   OGBX_CHECK(ring->steps >= 1, OGBX_EINVAL, who + "the ring is empty (steps must be >= 1)");
   OGBX_CHECK(total > 0, OGBX_EINVAL, who + "total must be > 0");
-  OGBX_CHECK(hcfg->hv_mask_table && hcfg->hv_reward_table && hcfg->lv_mask_table && hcfg->lv_reward_table, OGBX_EINVAL,
-             who + "missing reward/mask tables");
-  OGBX_CHECK(hcfg->value_subgoal_steps >= 1 && hcfg->low_subgoal_steps >= 1 && hcfg->actor_subgoal_steps >= 1,
-             OGBX_EINVAL, who + "subgoal steps must be >= 1");
-  OGBX_CHECK(!hcfg->has_low_value_goals || (hcfg->low_discount > 0.0 && hcfg->low_discount < 1.0), OGBX_EINVAL,
-             who + "low_discount must be in (0, 1)");
-  OGBX_CHECK(out->high_value_offsets && out->high_value_subgoal_steps && out->high_value_masks &&
-                 out->high_value_rewards && out->low_value_subgoal_steps && out->low_value_masks &&
-                 out->low_value_rewards && out->masks && out->rewards,
-             OGBX_EINVAL, who + "missing scalar output");
+  GC_TRY(check_hgc_config(hcfg, name, 1, "subgoal steps must be >= 1"));
+  GC_TRY(check_hgc_outputs(out, name));
   OGBX_CHECK(num_cols >= 0 && num_cols <= kGcMaxCols, OGBX_EINVAL, who + "0 to 32 columns");
   OGBX_CHECK(num_cols == 0 || cols, OGBX_EINVAL, who + "null columns");
   bool flat4;
   // every selector but next (1); the table is copied by launch_online_hgc, at the size it launches with
-  GC_TRY(check_gather_columns<true>(cols, num_cols, selects_up_to(kHgcSel - 1) & ~0b10u, "ogbx_online_hgc_sample",
+  GC_TRY(check_gather_columns<true>(cols, num_cols, selects_up_to(kHgcSel - 1) & ~0b10u, name,
                                     (GcColumns*)nullptr, &flat4));
-  const int64_t tile = gc_tile(total);
-  OGBX_CHECK((total + tile - 1) / tile <= 0x7fffffffll, OGBX_EINVAL, who + "too many samples for one launch");
+  int64_t tile, blocks;
+  OGBX_CHECK(sample_grid(total, &tile, &blocks), OGBX_EINVAL, who + "too many samples for one launch");
 
   const OnlineView v = online_view(*ring);
   const GcParams pr = gc_params(seed, *cfg, hcfg);
@@ -235,10 +230,10 @@ ogbx_status ogbx_online_hgc_sample(const ogbx_online_ring* ring, const ogbx_gc_c
   const ogbx_hgc_draw_record rec = record ? *record : ogbx_hgc_draw_record{};
   // the kernel arguments grow the host's launch cost (gc_device.h kGcSmallCols)
   if (num_cols <= kGcSmallCols)
-    return launch_online_hgc<GcColumnsSmall>(v, *cfg, *hcfg, pr, cols, num_cols, flat4, total, call_index, dr, rec,
-                                             *out, (hipStream_t)stream);
-  return launch_online_hgc<GcColumns>(v, *cfg, *hcfg, pr, cols, num_cols, flat4, total, call_index, dr, rec, *out,
-                                      (hipStream_t)stream);
+    return launch_online_hgc<GcColumnsSmall>(v, *cfg, *hcfg, pr, cols, num_cols, flat4, total, tile, blocks,
+                                             call_index, dr, rec, *out, (hipStream_t)stream);
+  return launch_online_hgc<GcColumns>(v, *cfg, *hcfg, pr, cols, num_cols, flat4, total, tile, blocks, call_index, dr,
+                                      rec, *out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -16,7 +16,8 @@
 // online_trl_sample_kernel is organised as online_gc_sample_kernel
 // (online.hip) and trl_sample_kernel (trl.hip): tiles of at most 64 samples
 // numbered XCD-major, the first wave runs the draw chains into LDS selectors,
-// then the whole workgroup copies rows.  A pick j of the table becomes a row by
+// then the whole workgroup copies rows (prologue: gc_device.h; bad-sample count,
+// record check, pointer list: trl_device.h).  A pick j of the table becomes a row by
 // select_pair: a search over P for the env, then a search over the env's live
 // closed episodes (ep_end) for the terminal rows before the pick.  The sample's
 // pick and the actor side's random goal are two independent chains; both
@@ -34,7 +35,7 @@
 #include "common.h"
 #include "gc_device.h"
 #include "online_device.h"
-#include "visual_tile.h"
+#include "trl_device.h"
 
 namespace ogbx {
 
@@ -152,30 +153,21 @@ __global__ void __launch_bounds__(256) online_trl_sample_kernel(
     const int b = (int)threadIdx.x % n_here;
     const bool own = (int)threadIdx.x < n_here;
     const int64_t s = base + b;
-    const uint64_t su = (uint64_t)s;
-    const uint32_t c0 = (uint32_t)su, c3 = (uint32_t)(su >> 32) ^ call_hi;
-    u32x4 w0, w1, w2, w3, w4;
-    if (!kInj && kGcSpread) {
-      w0 = tile_word(wb, 0, b), w1 = tile_word(wb, 1, b), w2 = tile_word(wb, 2, b), w3 = tile_word(wb, 3, b),
-      w4 = tile_word(wb, 4, b);
-    } else {
-      w0 = philox4x32_10({c0, call_lo, 0u, c3}, k0, k1);
-      w1 = philox4x32_10({c0, call_lo, 1u, c3}, k0, k1);
-      w2 = philox4x32_10({c0, call_lo, 2u, c3}, k0, k1);
-      w3 = philox4x32_10({c0, call_lo, 3u, c3}, k0, k1);
-      w4 = philox4x32_10({c0, call_lo, 4u, c3}, k0, k1);
-    }
+    u32x4 w[5];
+    sample_words<kInj || !kGcSpread>(wb, b, s, call_lo, call_hi, k0, k1, w);
     // the slot layout of trl_sample_kernel over a pick table of P[N] entries;
     // an empty table draws over one entry (every sample is then counted bad)
     const int64_t rows = ring.npick;  // L * N
     const int64_t table = tab.P[ring.n];
     const int64_t npick = table < 1 ? 1 : table;
     const bool given = kInj && dr.idxs != nullptr;
+    // written out, not root_picks: it moves this kernel (profiles/sampler_device_refactor_isa.txt)
     int64_t pick = -1;
-    if (!given) pick = (kInj && dr.pick) ? clamp_row(dr.pick[s], npick) : (int64_t)bounded64(w0.x, w0.y, (uint64_t)npick);
+    if (!given)
+      pick = (kInj && dr.pick) ? clamp_row(dr.pick[s], npick) : (int64_t)bounded64(w[0].x, w[0].y, (uint64_t)npick);
     GoalDraws v, a;
-    v.pick = (kInj && dr.v_pick) ? clamp_row(dr.v_pick[s], npick) : (int64_t)bounded64(w0.z, w0.w, (uint64_t)npick);
-    a.pick = (kInj && dr.a_pick) ? clamp_row(dr.a_pick[s], npick) : (int64_t)bounded64(w1.x, w1.y, (uint64_t)npick);
+    v.pick = (kInj && dr.v_pick) ? clamp_row(dr.v_pick[s], npick) : (int64_t)bounded64(w[0].z, w[0].w, (uint64_t)npick);
+    a.pick = (kInj && dr.a_pick) ? clamp_row(dr.a_pick[s], npick) : (int64_t)bounded64(w[1].x, w[1].y, (uint64_t)npick);
     // an injected midpoint row: loaded with the index loads, not after them
     const int64_t mid_given = (kInj && mid_in) ? mid_in[s] : 0;
     PickedRow pr, ar;
@@ -191,7 +183,7 @@ __global__ void __launch_bounds__(256) online_trl_sample_kernel(
     const int64_t prow = phys_row(ring, pr.e, pr.k);
     const int64_t final_idx = episode_end_flat(ring, pr.ep, idx, pr.e, pr.k);
     const int64_t a_rand = ar.e * ring.live + ar.k;
-    goal_side_draws<kInj>(dr, cfg, s, w1, w2, w3, w4, v_log_q, a_log_q, v, a);
+    goal_side_draws<kInj>(dr, cfg, s, w[1], w[2], w[3], w[4], v_log_q, a_log_q, v, a);
     // the value side has no random goal (the host refuses such a cfg); only an
     // injected u_traj >= 1 reaches its slot, and then counts as bad
     int64_t vg = sample_goal(idx, final_idx, v, idx, cfg.value_p_curgoal, cfg.value_traj_thresh,
@@ -206,12 +198,9 @@ __global__ void __launch_bounds__(256) online_trl_sample_kernel(
     const int64_t span = vg - idx;
     const bool bad = span <= 0 || table < 1;
     int64_t mid = idx;
-    if (!bad) mid = (kInj && mid_in) ? clamp_row(mid_given, rows) : idx + (int64_t)bounded64(w4.z, w4.w, (uint64_t)span);
-    if (o.bad_count) {  // every lane of the wave is here: one atomic per tile at most
-      const unsigned long long m = __ballot(bad && own);
-      if (m != 0ull && threadIdx.x == 0)
-        atomicAdd(reinterpret_cast<unsigned long long*>(o.bad_count), (unsigned long long)__popcll(m));
-    }
+    if (!bad)
+      mid = (kInj && mid_in) ? clamp_row(mid_given, rows) : idx + (int64_t)bounded64(w[4].z, w[4].w, (uint64_t)span);
+    count_bad_samples(o.bad_count, bad, own);
     const int64_t next = idx + 1 < rows ? idx + 1 : rows - 1;
     const int64_t nrow = phys_of_flat(ring, next), vrow = phys_of_flat(ring, vg), arow = phys_of_flat(ring, ag),
                   mrow = phys_of_flat(ring, mid);
@@ -221,6 +210,7 @@ __global__ void __launch_bounds__(256) online_trl_sample_kernel(
       sel[2][b] = vrow;
       sel[3][b] = arow;
       sel[4][b] = mrow;
+      // written out, as the midpoint: one helper moved either TRL kernel (profiles/sampler_device_refactor_isa.txt)
       if (o.idxs) o.idxs[s] = idx;
       if (o.value_goal_idxs) o.value_goal_idxs[s] = vg;
       if (o.actor_goal_idxs) o.actor_goal_idxs[s] = ag;
@@ -289,25 +279,15 @@ ogbx_status ogbx_online_trl_sample(const ogbx_online_ring* ring, const int64_t* 
   GC_TRY(check_columns(cols, num_cols, total, 1, OGBX_TRL_SELECT_MIDPOINT, name, &cc, &flat4));
   const ogbx_gc_draws dr = draws ? *draws : ogbx_gc_draws{};
   const ogbx_gc_draw_record rec = record ? *record : ogbx_gc_draw_record{};
-  OGBX_CHECK(!rec.pick || (rec.v_pick && rec.v_geom && rec.v_dist && rec.v_u_traj && rec.v_u_cur && rec.a_pick &&
-                           rec.a_geom && rec.a_dist && rec.a_u_traj && rec.a_u_cur),
-             OGBX_EINVAL, who + "incomplete draw record");
-  const int64_t tile = gc_tile(total), blocks = (total + tile - 1) / tile;
-  OGBX_CHECK(blocks <= 0x7fffffffll, OGBX_EINVAL, who + "too many samples for one launch");
+  GC_TRY(check_draw_record_complete(rec, name));
+  int64_t tile, blocks;
+  OGBX_CHECK(sample_grid(total, &tile, &blocks), OGBX_EINVAL, who + "too many samples for one launch");
 
   int dev = 0;
   OGBX_HIP(hipGetDevice(&dev));
-  bool ok = on_device(P, dev) && on_device(ring->ep_seq, dev) && on_device(ring->cur_seq, dev) &&
-            on_device(ring->ep_end, dev);
-  const void* opt[] = {midpoint, midpoint_record, dr.idxs, dr.pick, dr.v_pick, dr.v_geom, dr.v_dist, dr.v_u_traj,
-                       dr.v_u_cur, dr.a_pick, dr.a_geom, dr.a_dist, dr.a_u_traj, dr.a_u_cur, rec.pick, rec.v_pick,
-                       rec.v_geom, rec.v_dist, rec.v_u_traj, rec.v_u_cur, rec.a_pick, rec.a_geom, rec.a_dist,
-                       rec.a_u_traj, rec.a_u_cur, out->idxs, out->value_goal_idxs, out->actor_goal_idxs,
-                       out->value_midpoint_idxs, out->value_offsets, out->value_midpoint_offsets, out->masks,
-                       out->rewards, out->bad_count};
-  for (const void* q : opt) ok = ok && (!q || on_device(q, dev));
-  for (int i = 0; i < num_cols; ++i) ok = ok && on_device(cols[i].src, dev) && on_device(cols[i].dst, dev);
-  OGBX_CHECK(ok, OGBX_EINVAL, who + "every pointer must be device memory of the current device");
+  OGBX_CHECK(all_on_device(dev, {P, ring->ep_seq, ring->cur_seq, ring->ep_end}) &&
+                 trl_pointers_on_device(dev, dr, rec, *out, midpoint, midpoint_record, cols, num_cols),
+             OGBX_EINVAL, who + "every pointer must be device memory of the current device");
 
   const OnlineView v = online_view(*ring);
   OnlineTrlTable tab{P, 0};

@@ -163,79 +163,23 @@ ogbx_status ogbx_online_visual_gather(const ogbx_online_ring* ring, const ogbx_h
   if (ogbx_status st = check_ring(ring, who)) return st;
   OGBX_CHECK(cols && indices, OGBX_EINVAL, who + "null argument");
   OGBX_CHECK(ring->steps >= 1, OGBX_EINVAL, who + "the ring is empty (steps must be >= 1)");
-  OGBX_CHECK(indices->idxs, OGBX_EINVAL, who + "indices->idxs is required");
-  OGBX_CHECK(num_cols >= 1 && num_cols <= OGBX_VISUAL_MAX_COLS, OGBX_EINVAL, who + "1 to 16 columns");
-  OGBX_CHECK(total > 0, OGBX_EINVAL, who + "total must be > 0");
-  OGBX_CHECK(frame_stack >= 1 && frame_stack <= OGBX_VISUAL_MAX_STACK, OGBX_EINVAL,
-             who + "frame_stack must be in 1..8");
-  OGBX_CHECK(padding >= 0 && padding < (1 << 20), OGBX_EINVAL, who + "padding must be >= 0");
-  OGBX_CHECK(!crop_out || crop_from || draw_crop, OGBX_EINVAL, who + "crop_out without crop offsets");
-  if (hcfg)
-    OGBX_CHECK(hcfg->value_subgoal_steps >= 0 && hcfg->low_subgoal_steps >= 0 && hcfg->actor_subgoal_steps >= 0,
-               OGBX_EINVAL, who + "negative subgoal steps");
-  const int max_select = hcfg ? kHgcSel - 1 : 3;
   OnVisColumns vc{};
-  uint32_t lds = 16;
-  for (int i = 0; i < num_cols; ++i) {
-    const ogbx_online_visual_column& c = cols[i];
-    OGBX_CHECK(c.src && c.dst, OGBX_EINVAL, who + "null column pointer");
-    OGBX_CHECK(c.height > 0 && c.width > 0 && c.px_bytes > 0, OGBX_EINVAL, who + "bad image shape");
-    // the ring stores its own next_observations: no next-row selector
-    OGBX_CHECK(c.select >= 0 && c.select <= max_select && c.select != 1, OGBX_EINVAL,
-               who + "selector out of range");
-    const int s = c.select;
-    const bool need_v = s == 2 || s == 4 || s == 5, need_a = s == 3 || s == 7 || s == 9, need_l = s == 6;
-    OGBX_CHECK((!need_v || indices->value_goal_idxs) && (!need_a || indices->actor_goal_idxs) &&
-                   (!need_l || indices->low_value_goal_idxs),
-               OGBX_EINVAL, who + "a column selects through a missing index output");
-    const int64_t F = c.stack ? frame_stack : 1;
-    const int64_t row_bytes = (int64_t)c.width * c.px_bytes, frame = row_bytes * c.height;
-    OGBX_CHECK(frame * F <= (1ll << 30), OGBX_EINVAL, who + "image too large");
-    lds = std::max<uint32_t>(lds, vis_lds_bytes(frame, F));
-    vc.c[i] = c;
-  }
-  for (int i = 0; i < num_cols; ++i) {  // at least one image row per staged frame
-    const uint32_t F = cols[i].stack ? (uint32_t)frame_stack : 1u;
-    OGBX_CHECK((int64_t)((lds / F) & ~15u) >= (int64_t)cols[i].width * cols[i].px_bytes, OGBX_EINVAL,
-               who + "image row too wide to stage");
-  }
-  const int64_t blocks = ((total + 7) / 8) * 8 * num_cols;
-  OGBX_CHECK(blocks <= 0x7fffffffll, OGBX_EINVAL, who + "too many (sample, column) pairs for one launch");
+  uint32_t lds;
+  int64_t blocks;
+  const VisualCall v{indices,   hcfg,      total,    num_cols, frame_stack, padding,
+                     crop_from, draw_crop, crop_out, seed,     call_index};
+  GC_TRY(check_visual_gather(who, v, cols, 1, "1 to 16 columns", false, &vc, &lds, &blocks));
 
   int dev = 0;
   OGBX_HIP(hipGetDevice(&dev));
-  bool ok = on_device(ring->ep_seq, dev) && on_device(ring->cur_seq, dev) && on_device(ring->ep_end, dev) &&
-            on_device(indices->idxs, dev);
-  for (const int64_t* q : {indices->value_goal_idxs, indices->actor_goal_idxs, indices->low_value_goal_idxs,
-                           crop_from, (const int64_t*)crop_out})
-    ok = ok && (!q || on_device(q, dev));
-  for (int i = 0; i < num_cols; ++i)
-    ok = ok && on_device(cols[i].src, dev) && on_device(cols[i].dst, dev) &&
-         (!cols[i].alt || on_device(cols[i].alt, dev));
+  bool ok = all_on_device(dev, {ring->ep_seq, ring->cur_seq, ring->ep_end}) &&
+            visual_pointers_on_device(dev, v, cols);
+  for (int i = 0; i < num_cols && ok; ++i) ok = all_on_device(dev, {cols[i].alt});
   OGBX_CHECK(ok, OGBX_EINVAL, who + "every pointer must be device memory of the current device");
 
   OnVisArgs a{};
   a.ring = online_view(*ring);
-  a.idxs = indices->idxs;
-  a.vg = indices->value_goal_idxs;
-  a.ag = indices->actor_goal_idxs;
-  a.lvg = indices->low_value_goal_idxs;
-  if (hcfg) {
-    a.k_value = hcfg->value_subgoal_steps;
-    a.k_low = hcfg->low_subgoal_steps;
-    a.k_actor = hcfg->actor_subgoal_steps;
-  }
-  a.frame_stack = frame_stack;
-  a.padding = padding;
-  a.draw = draw_crop != 0 && !crop_from;
-  a.crop_from = crop_from;
-  a.crop_out = crop_out;
-  seed_key(seed, hcfg ? kTagHgcSample : kTagGcSample, &a.k0, &a.k1);
-  a.call_lo = (uint32_t)call_index;
-  a.call_hi = (uint32_t)(call_index >> 32);
-  a.lds_bytes = lds;
-  a.num_cols = num_cols;
-  a.total = total;
+  fill_visual_args(a, v, lds);
   hipLaunchKernelGGL(online_visual_gather_kernel, dim3((uint32_t)blocks), dim3(kVisThreads), lds,
                      (hipStream_t)stream, a, vc);
   OGBX_LAUNCHED("online_visual_gather_kernel");

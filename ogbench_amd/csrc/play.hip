@@ -197,15 +197,6 @@ __global__ void __launch_bounds__(256) play_semantic_kernel(int32_t ne, int32_t 
   out[3 * e + 2] = (int32_t)bounded_u32(w.z, (uint32_t)xy);
 }
 
-static bool play_on_device(const void* ptr, int device) {
-  hipPointerAttribute_t attr{};
-  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return attr.type == hipMemoryTypeDevice && attr.device == device;
-}
-
 }  // namespace ogbx
 
 using namespace ogbx;
@@ -239,10 +230,8 @@ ogbx_status ogbx_play_plan(const ogbx_play_config* cfg, int64_t n_envs, int32_t 
   const ogbx_play_outputs o = out ? *out : ogbx_play_outputs{};
   int dev = 0;
   OGBX_HIP(hipGetDevice(&dev));
-  bool ok = play_on_device(actions, dev);
-  if (tape && tape->tape) ok = ok && play_on_device(tape->tape, dev) && play_on_device(tape->short_count, dev);
-  for (const void* q : {(const void*)o.used, (const void*)o.decisions, (const void*)o.terminals})
-    ok = ok && (!q || play_on_device(q, dev));
+  bool ok = on_device(actions, dev) && all_on_device(dev, {o.used, o.decisions, o.terminals});
+  if (tape && tape->tape) ok = ok && on_device(tape->tape, dev) && on_device(tape->short_count, dev);
   OGBX_CHECK(ok, OGBX_EINVAL, who + "every pointer must be device memory of the current device");
 
   PlayArgs a{};
@@ -273,7 +262,7 @@ ogbx_status ogbx_play_sample_semantic(int32_t num_elems, int32_t xy_size, int64_
   OGBX_CHECK(env_base >= 0, OGBX_EINVAL, who + "env_base must be >= 0");
   int dev = 0;
   OGBX_HIP(hipGetDevice(&dev));
-  OGBX_CHECK(play_on_device(out, dev), OGBX_EINVAL, who + "out must be device memory of the current device");
+  OGBX_CHECK(on_device(out, dev), OGBX_EINVAL, who + "out must be device memory of the current device");
   uint32_t k0, k1;
   seed_key(seed, kTagPlayPlan, &k0, &k1);
   hipLaunchKernelGGL(play_semantic_kernel, dim3((uint32_t)((n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream,

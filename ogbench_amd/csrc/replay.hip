@@ -27,7 +27,6 @@
 #include "common.h"
 #include "gc_device.h"
 #include "replay_device.h"
-#include "visual_tile.h"
 
 namespace ogbx {
 
@@ -206,9 +205,8 @@ ogbx_status ogbx_replay_insert(int64_t* header, int32_t parity, int64_t max_size
   if (ogbx_status st = check_insert_columns(cols, num_cols, alt_select, who)) return st;
   int dev = 0;
   OGBX_HIP(hipGetDevice(&dev));
-  bool ok = on_device(header, dev) && (!keep || on_device(keep, dev)) && (!alt_select || on_device(alt_select, dev));
-  for (int i = 0; i < num_cols && ok; ++i)
-    ok = on_device(cols[i].dst, dev) && on_device(cols[i].src, dev) && (!cols[i].alt || on_device(cols[i].alt, dev));
+  bool ok = all_on_device(dev, {header, keep, alt_select});
+  for (int i = 0; i < num_cols && ok; ++i) ok = all_on_device(dev, {cols[i].dst, cols[i].src, cols[i].alt});
   OGBX_CHECK(ok, OGBX_EINVAL, who + "every pointer must be device memory of the current device");
 
   hipStream_t s = (hipStream_t)stream;
@@ -242,14 +240,12 @@ ogbx_status ogbx_replay_sample(const int64_t* header, int32_t parity, int64_t ma
   GcColumnsSmall cc{};
   bool flat4;
   GC_TRY(check_gather_columns<true>(cols, num_cols, 0b11u, "ogbx_replay_sample", &cc, &flat4));  // idx, next
-  const int64_t tile = gc_tile(total);
-  const int64_t blocks = (total + tile - 1) / tile;
-  OGBX_CHECK(blocks <= 0x7fffffffll, OGBX_EINVAL, who + "too many samples for one launch");
+  int64_t tile, blocks;
+  OGBX_CHECK(sample_grid(total, &tile, &blocks), OGBX_EINVAL, who + "too many samples for one launch");
   int dev = 0;
   OGBX_HIP(hipGetDevice(&dev));
-  bool ok = on_device(header, dev) && (!idxs || on_device(idxs, dev)) && (!idxs_out || on_device(idxs_out, dev)) &&
-            (!empty_count || on_device(empty_count, dev));
-  for (int i = 0; i < num_cols && ok; ++i) ok = on_device(cols[i].src, dev) && on_device(cols[i].dst, dev);
+  bool ok = all_on_device(dev, {header, idxs, idxs_out, empty_count});
+  for (int i = 0; i < num_cols && ok; ++i) ok = all_on_device(dev, {cols[i].src, cols[i].dst});
   OGBX_CHECK(ok, OGBX_EINVAL, who + "every pointer must be device memory of the current device");
 
   uint32_t k0, k1;

@@ -7,7 +7,8 @@
 //   GCDataset.sample, TRL branch              254-292
 //
 // trl_sample_kernel is organised as gc_sample_kernel (gcsample.hip) and built
-// from the same device code (gc_device.h): tiles of at most 64 samples
+// from the same device code (gc_device.h; trl_device.h holds what it shares with
+// the ring's online_trl_sample_kernel alone): tiles of at most 64 samples
 // numbered XCD-major, the first wave runs the draw chain into LDS selectors,
 // then the whole workgroup copies rows.  The fifth selector, the midpoint, is
 // arithmetic on idx and the value goal -- mid = idx + mulhi(u64, goal - idx)
@@ -20,6 +21,7 @@
 #include "../../include/ogbx_trl.h"
 #include "common.h"
 #include "gc_device.h"
+#include "trl_device.h"
 
 namespace ogbx {
 
@@ -43,34 +45,20 @@ __global__ void __launch_bounds__(256) trl_sample_kernel(
     const int b = (int)threadIdx.x % n_here;
     const bool own = (int)threadIdx.x < n_here;
     const int64_t s = base + b;
-    const uint64_t su = (uint64_t)s;
-    const uint32_t c0 = (uint32_t)su, c3 = (uint32_t)(su >> 32) ^ call_hi;
-    u32x4 w0, w1, w2, w3, w4;
-    if (!kInj && kGcSpread) {
-      w0 = tile_word(wb, 0, b), w1 = tile_word(wb, 1, b), w2 = tile_word(wb, 2, b), w3 = tile_word(wb, 3, b),
-      w4 = tile_word(wb, 4, b);
-    } else {
-      w0 = philox4x32_10({c0, call_lo, 0u, c3}, k0, k1);
-      w1 = philox4x32_10({c0, call_lo, 1u, c3}, k0, k1);
-      w2 = philox4x32_10({c0, call_lo, 2u, c3}, k0, k1);
-      w3 = philox4x32_10({c0, call_lo, 3u, c3}, k0, k1);
-      w4 = philox4x32_10({c0, call_lo, 4u, c3}, k0, k1);
-    }
+    u32x4 w[5];
+    sample_words<kInj || !kGcSpread>(wb, b, s, call_lo, call_hi, k0, k1, w);
     // the GC chain, word for word as gc_sample_kernel draws it
     const int64_t npick = buf.valid_idxs ? buf.num_valid : buf.num_rows;
-    int64_t idx = 0, pick = -1, final_idx;
-    if (kInj && dr.idxs) idx = dr.idxs[s];
-    else pick = (kInj && dr.pick) ? dr.pick[s] : (int64_t)bounded64(w0.x, w0.y, (uint64_t)npick);
+    int64_t idx = 0, pick, final_idx;
     GoalDraws v, a;
-    v.pick = (kInj && dr.v_pick) ? dr.v_pick[s] : (int64_t)bounded64(w0.z, w0.w, (uint64_t)npick);
-    a.pick = (kInj && dr.a_pick) ? dr.a_pick[s] : (int64_t)bounded64(w1.x, w1.y, (uint64_t)npick);
+    root_picks<kInj, false>(dr, s, w[0], w[1], npick, buf.num_rows, &idx, &pick, &v.pick, &a.pick);
     // an injected midpoint row: loaded with the index loads, not after them
     const int64_t mid_given = (kInj && mid_in) ? mid_in[s] : 0;
     index_loads(buf, kInj && dr.idxs != nullptr, pick, &idx, &final_idx);
     const int64_t v_rand = cfg.value_cur_is_one ? 0 : rand_goal_of(buf, v.pick);
     const int64_t a_rand = cfg.actor_cur_is_one ? 0 : rand_goal_of(buf, a.pick);
     const int64_t next = idx + 1 < buf.num_rows ? idx + 1 : buf.num_rows - 1;
-    goal_side_draws<kInj>(dr, cfg, s, w1, w2, w3, w4, v_log_q, a_log_q, v, a);
+    goal_side_draws<kInj>(dr, cfg, s, w[1], w[2], w[3], w[4], v_log_q, a_log_q, v, a);
     const int64_t vg = sample_goal(idx, final_idx, v, v_rand, cfg.value_p_curgoal,
                                    cfg.value_traj_thresh, cfg.value_geom_sample, cfg.value_cur_is_one);
     const int64_t ag = sample_goal(idx, final_idx, a, a_rand, cfg.actor_p_curgoal,
@@ -85,31 +73,28 @@ __global__ void __launch_bounds__(256) trl_sample_kernel(
       if (kInj && mid_in)
         mid = mid_given < 0 ? 0 : (mid_given >= buf.num_rows ? buf.num_rows - 1 : mid_given);
       else
-        mid = idx + (int64_t)bounded64(w4.z, w4.w, (uint64_t)span);
+        mid = idx + (int64_t)bounded64(w[4].z, w[4].w, (uint64_t)span);
     }
-    if (o.bad_count) {  // every lane of the wave is here: one atomic per tile at most
-      const unsigned long long m = __ballot(bad && own);
-      if (m != 0ull && threadIdx.x == 0)
-        atomicAdd(reinterpret_cast<unsigned long long*>(o.bad_count), (unsigned long long)__popcll(m));
-    }
+    count_bad_samples(o.bad_count, bad, own);
     if (own) {
-    sel[0][b] = idx;
-    sel[1][b] = next;
-    sel[2][b] = vg;
-    sel[3][b] = ag;
-    sel[4][b] = mid;
-    if (o.idxs) o.idxs[s] = idx;
-    if (o.value_goal_idxs) o.value_goal_idxs[s] = vg;
-    if (o.actor_goal_idxs) o.actor_goal_idxs[s] = ag;
-    if (o.value_midpoint_idxs) o.value_midpoint_idxs[s] = mid;
-    if (o.value_offsets) o.value_offsets[s] = span;
-    if (o.value_midpoint_offsets) o.value_midpoint_offsets[s] = mid - idx;
-    const double succ = idx == vg ? 1.0 : 0.0;
-    if (o.masks) o.masks[s] = 1.0 - succ;
-    if (o.rewards) o.rewards[s] = succ - (cfg.gc_negative ? 1.0 : 0.0);
-    if (mid_rec) mid_rec[s] = mid;
-    store_draw_record(rec, s, pick, v, a);
-    }  // own
+      sel[0][b] = idx;
+      sel[1][b] = next;
+      sel[2][b] = vg;
+      sel[3][b] = ag;
+      sel[4][b] = mid;
+      // written out, as the midpoint: one helper moved either TRL kernel (profiles/sampler_device_refactor_isa.txt)
+      if (o.idxs) o.idxs[s] = idx;
+      if (o.value_goal_idxs) o.value_goal_idxs[s] = vg;
+      if (o.actor_goal_idxs) o.actor_goal_idxs[s] = ag;
+      if (o.value_midpoint_idxs) o.value_midpoint_idxs[s] = mid;
+      if (o.value_offsets) o.value_offsets[s] = span;
+      if (o.value_midpoint_offsets) o.value_midpoint_offsets[s] = mid - idx;
+      const double succ = idx == vg ? 1.0 : 0.0;
+      if (o.masks) o.masks[s] = 1.0 - succ;
+      if (o.rewards) o.rewards[s] = succ - (cfg.gc_negative ? 1.0 : 0.0);
+      if (mid_rec) mid_rec[s] = mid;
+      store_draw_record(rec, s, pick, v, a);
+    }
   }
   __syncthreads();
   copy_tile<0>(cols, num_cols, sel, base, n_here, flat4);
@@ -119,16 +104,6 @@ struct NotTrajEnd {
   const int64_t* traj_end;
   __device__ bool operator()(const int64_t& r) const { return traj_end[r] != r; }
 };
-
-// Device memory of `device`?
-static bool trl_on_device(const void* ptr, int device) {
-  hipPointerAttribute_t attr{};
-  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return attr.type == hipMemoryTypeDevice && attr.device == device;
-}
 
 }  // namespace ogbx
 
@@ -151,27 +126,18 @@ ogbx_status ogbx_trl_sample(const ogbx_gc_buffer* buf, const ogbx_gc_config* cfg
   GC_TRY(check_buffer(buf));
   const ogbx_gc_draws dr = draws ? *draws : ogbx_gc_draws{};
   const ogbx_gc_draw_record rec = record ? *record : ogbx_gc_draw_record{};
-  OGBX_CHECK(!rec.pick || (rec.v_pick && rec.v_geom && rec.v_dist && rec.v_u_traj && rec.v_u_cur && rec.a_pick &&
-                           rec.a_geom && rec.a_dist && rec.a_u_traj && rec.a_u_cur),
-             OGBX_EINVAL, named(who, "incomplete draw record"));
+  GC_TRY(check_draw_record_complete(rec, who));
 
   int dev = 0;
   OGBX_HIP(hipGetDevice(&dev));
-  bool ok = trl_on_device(buf->traj_end, dev);
-  const void* opt[] = {buf->valid_idxs, buf->valid_traj_end, buf->valid_pairs, midpoint, midpoint_record,
-                       dr.idxs, dr.pick, dr.v_pick, dr.v_geom, dr.v_dist, dr.v_u_traj, dr.v_u_cur, dr.a_pick,
-                       dr.a_geom, dr.a_dist, dr.a_u_traj, dr.a_u_cur, rec.pick, rec.v_pick, rec.v_geom,
-                       rec.v_dist, rec.v_u_traj, rec.v_u_cur, rec.a_pick, rec.a_geom, rec.a_dist, rec.a_u_traj,
-                       rec.a_u_cur, out->idxs, out->value_goal_idxs, out->actor_goal_idxs,
-                       out->value_midpoint_idxs, out->value_offsets, out->value_midpoint_offsets, out->masks,
-                       out->rewards, out->bad_count};
-  for (const void* q : opt) ok = ok && (!q || trl_on_device(q, dev));
-  for (int i = 0; i < num_cols; ++i) ok = ok && trl_on_device(cols[i].src, dev) && trl_on_device(cols[i].dst, dev);
-  OGBX_CHECK(ok, OGBX_EINVAL, named(who, "every pointer must be device memory of the current device"));
+  OGBX_CHECK(all_on_device(dev, {buf->traj_end, buf->valid_idxs, buf->valid_traj_end, buf->valid_pairs}) &&
+                 trl_pointers_on_device(dev, dr, rec, *out, midpoint, midpoint_record, cols, num_cols),
+             OGBX_EINVAL, named(who, "every pointer must be device memory of the current device"));
 
   const GcParams pr = gc_params(seed, *cfg, nullptr);  // the GC stream tag: same words as ogbx_gc_sample
   const int64_t total = batch * num_batches;
-  const int64_t tile = gc_tile(total), blocks = (total + tile - 1) / tile;
+  int64_t tile, blocks;
+  sample_grid(total, &tile, &blocks);
   const auto kern = (any_draw(dr) || midpoint) ? trl_sample_kernel<true> : trl_sample_kernel<false>;
   hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, *buf, *cfg, cc, num_cols,
                      total, (int)tile, dr, midpoint, pr.k0, pr.k1, (uint32_t)call_index,

@@ -5,15 +5,21 @@
 // F * px_bytes bytes, shifted by the crop -- from LDS in 16-byte units aligned
 // to the destination.  compose_frames takes the address of each block's frame,
 // so the unrelated physical rows of the episode ring compose with the code of
-// the offline datasets' consecutive rows (compose_image).  Internal to
+// the offline datasets' consecutive rows (compose_image).  The two gathers
+// over (sample, column) pairs (visual.hip, online_visual.hip) also take their
+// host path from here.  Internal to
 // libogbx.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <string>
+
 #include "../../include/ogbx_visual.h"
 #include "common.h"
+#include "gc_select.h"
 
 namespace ogbx {
 
@@ -28,7 +34,6 @@ struct VisGeom {
   int32_t px_bytes;  // bytes of one pixel of ONE frame
 };
 
-__device__ inline int64_t clamp_row(int64_t r, int64_t R) { return r < 0 ? 0 : (r >= R ? R - 1 : r); }
 __device__ inline int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // Global -> LDS (or global) copy of len bytes by the whole workgroup: 16-byte
@@ -183,21 +188,109 @@ __device__ __forceinline__ void crop_offsets(const int64_t* __restrict__ crop_fr
 }
 
 // ---------------------------------------------------------------- host side
-// Device memory of `device`?
-static bool on_device(const void* ptr, int device) {
-  hipPointerAttribute_t attr{};
-  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return attr.type == hipMemoryTypeDevice && attr.device == device;
-}
-
 // Dynamic LDS for images of `frame` bytes stacked F deep: all F frames padded
 // to 16 bytes when they fit the budget, else the budget (the band loop).
 static uint32_t vis_lds_bytes(int64_t frame, int64_t F) {
   const int64_t need = F * ((frame + 15) & ~15ll);
   return (uint32_t)(need < (int64_t)kVisLdsMax ? need : (int64_t)kVisLdsMax);
+}
+
+// What a gather call passes besides its buffer and columns.
+struct VisualCall {
+  const ogbx_visual_indices* indices;
+  const ogbx_hgc_config* hcfg;
+  int64_t total;
+  int32_t num_cols, frame_stack, padding;
+  const int64_t* crop_from;
+  int32_t draw_crop;
+  int64_t* crop_out;
+  uint64_t seed, call_index;
+};
+
+// The argument checks the two gathers share, from indices->idxs on, in their
+// order; copies the columns into the kernel argument table and gives the launch
+// its dynamic LDS and grid.  min_cols, count_words: the entry point's column
+// count and its wording; next_selector: select code 1 is allowed (not over the
+// ring, which stores its own next_observations).
+template <class Col, class Table>
+static ogbx_status check_visual_gather(const std::string& who, const VisualCall& v, const Col* cols, int min_cols,
+                                       const char* count_words, bool next_selector, Table* table, uint32_t* lds_bytes,
+                                       int64_t* blocks) {
+  const ogbx_hgc_config* hcfg = v.hcfg;
+  const int32_t num_cols = v.num_cols, frame_stack = v.frame_stack;
+  OGBX_CHECK(v.indices->idxs, OGBX_EINVAL, who + "indices->idxs is required");
+  OGBX_CHECK(num_cols >= min_cols && num_cols <= OGBX_VISUAL_MAX_COLS, OGBX_EINVAL, who + count_words);
+  OGBX_CHECK(v.total > 0, OGBX_EINVAL, who + "total must be > 0");
+  OGBX_CHECK(frame_stack >= 1 && frame_stack <= OGBX_VISUAL_MAX_STACK, OGBX_EINVAL,
+             who + "frame_stack must be in 1..8");
+  OGBX_CHECK(v.padding >= 0 && v.padding < (1 << 20), OGBX_EINVAL, who + "padding must be >= 0");
+  OGBX_CHECK(!v.crop_out || v.crop_from || v.draw_crop, OGBX_EINVAL, who + "crop_out without crop offsets");
+  if (hcfg)
+    OGBX_CHECK(hcfg->value_subgoal_steps >= 0 && hcfg->low_subgoal_steps >= 0 && hcfg->actor_subgoal_steps >= 0,
+               OGBX_EINVAL, who + "negative subgoal steps");
+  const int max_select = hcfg ? kHgcSel - 1 : 3;
+  uint32_t lds = 16;
+  for (int i = 0; i < num_cols; ++i) {
+    const Col& c = cols[i];
+    OGBX_CHECK(c.src && c.dst, OGBX_EINVAL, who + "null column pointer");
+    OGBX_CHECK(c.height > 0 && c.width > 0 && c.px_bytes > 0, OGBX_EINVAL, who + "bad image shape");
+    OGBX_CHECK(c.select >= 0 && c.select <= max_select && (next_selector || c.select != 1), OGBX_EINVAL,
+               who + "selector out of range");
+    const int s = c.select;
+    const bool need_v = s == 2 || s == 4 || s == 5, need_a = s == 3 || s == 7 || s == 9, need_l = s == 6;
+    OGBX_CHECK((!need_v || v.indices->value_goal_idxs) && (!need_a || v.indices->actor_goal_idxs) &&
+                   (!need_l || v.indices->low_value_goal_idxs),
+               OGBX_EINVAL, who + "a column selects through a missing index output");
+    const int64_t F = c.stack ? frame_stack : 1;
+    const int64_t row_bytes = (int64_t)c.width * c.px_bytes, frame = row_bytes * c.height;
+    OGBX_CHECK(frame * F <= (1ll << 30), OGBX_EINVAL, who + "image too large");
+    lds = std::max<uint32_t>(lds, vis_lds_bytes(frame, F));
+    table->c[i] = c;
+  }
+  for (int i = 0; i < num_cols; ++i) {  // at least one image row per staged frame
+    const uint32_t F = cols[i].stack ? (uint32_t)frame_stack : 1u;
+    OGBX_CHECK((int64_t)((lds / F) & ~15u) >= (int64_t)cols[i].width * cols[i].px_bytes, OGBX_EINVAL,
+               who + "image row too wide to stage");
+  }
+  *blocks = ((v.total + 7) / 8) * 8 * num_cols;
+  OGBX_CHECK(*blocks <= 0x7fffffffll, OGBX_EINVAL, who + "too many (sample, column) pairs for one launch");
+  *lds_bytes = lds;
+  return OGBX_OK;
+}
+
+// The index outputs, the crop arrays and both ends of every column are device
+// memory of `dev` (a column's alt, where its type has one, is the caller's).
+template <class Col>
+static bool visual_pointers_on_device(int dev, const VisualCall& v, const Col* cols) {
+  bool ok = all_on_device(dev, {v.indices->idxs, v.indices->value_goal_idxs, v.indices->actor_goal_idxs,
+                                v.indices->low_value_goal_idxs, v.crop_from, v.crop_out});
+  for (int i = 0; i < v.num_cols && ok; ++i) ok = all_on_device(dev, {cols[i].src, cols[i].dst});
+  return ok;
+}
+
+// The fields VisArgs and OnVisArgs have in common, by name.
+template <class Args>
+static void fill_visual_args(Args& a, const VisualCall& v, uint32_t lds_bytes) {
+  a.idxs = v.indices->idxs;
+  a.vg = v.indices->value_goal_idxs;
+  a.ag = v.indices->actor_goal_idxs;
+  a.lvg = v.indices->low_value_goal_idxs;
+  if (v.hcfg) {
+    a.k_value = v.hcfg->value_subgoal_steps;
+    a.k_low = v.hcfg->low_subgoal_steps;
+    a.k_actor = v.hcfg->actor_subgoal_steps;
+  }
+  a.frame_stack = v.frame_stack;
+  a.padding = v.padding;
+  a.draw = v.draw_crop != 0 && !v.crop_from;
+  a.crop_from = v.crop_from;
+  a.crop_out = v.crop_out;
+  seed_key(v.seed, v.hcfg ? kTagHgcSample : kTagGcSample, &a.k0, &a.k1);
+  a.call_lo = (uint32_t)v.call_index;
+  a.call_hi = (uint32_t)(v.call_index >> 32);
+  a.lds_bytes = lds_bytes;
+  a.num_cols = v.num_cols;
+  a.total = v.total;
 }
 
 }  // namespace ogbx
