@@ -1,7 +1,8 @@
 // online_device.h -- what the sample kernels over the episode ring share
-// (online.hip, online_hgc.hip; include/ogbx_online.h): the ring as a kernel
-// argument, the flat-to-physical row map, the episode-end lookup, and the
-// host-side ring check.  Internal to libogbx.
+// (online.hip, online_hgc.hip, online_visual.hip, online_trl.hip,
+// online_atc.hip; include/ogbx_online.h): the ring as a kernel argument, the
+// flat-to-physical row map, the episode-end lookup, the first row of a frame
+// stack, and the host-side ring check.  Internal to libogbx.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +11,7 @@
 #include <string>
 
 #include "../../include/ogbx_online.h"
+#include "../../include/ogbx_visual.h"
 #include "common.h"
 
 namespace ogbx {
@@ -83,6 +85,27 @@ __device__ __forceinline__ int64_t episode_end_flat(const OnlineView& ring, cons
     end = end < step ? step : (end > ring.last ? ring.last : end);  // whatever the table holds
   }
   return idx + (end - step);  // same env: e * L + (end - first)
+}
+
+// The live offset of the first row of the stack of n frames that ends at
+// offset k of env e: the earliest of k - (n-1) .. k that is live (>= 0) and
+// has the row's ep_seq.  The ordinals load together (no load waits for a
+// compare); ep_seq does not decrease along an env's live steps, so the rows
+// of the episode are the run that ends at k.
+__device__ __forceinline__ int64_t stack_first(const OnlineView& ring, int64_t e, int64_t k, int n) {
+  if (n <= 1) return k;
+  int32_t seq[OGBX_VISUAL_MAX_STACK] = {};
+#pragma unroll
+  for (int i = 0; i < OGBX_VISUAL_MAX_STACK; ++i)
+    if (i < n && k - i >= 0) seq[i] = ring.ep_seq[phys_row(ring, e, k - i)];
+  int run = 0;  // rows before k that belong
+  bool open = true;
+#pragma unroll
+  for (int i = 1; i < OGBX_VISUAL_MAX_STACK; ++i) {
+    open = open && i < n && k - i >= 0 && seq[i] == seq[0];
+    run += open ? 1 : 0;
+  }
+  return k - run;
 }
 
 // ---------------------------------------------------------------- host side

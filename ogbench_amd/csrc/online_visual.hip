@@ -77,27 +77,6 @@ __device__ inline void select_ring_row(const OnVisArgs& a, int sel, int64_t s, i
   *k += steps;  // 0 <= steps <= fin - u, and fin <= e * L + L - 1
 }
 
-// The live offset of the first row of the stack of n frames that ends at
-// offset k of env e: the earliest of k - (n-1) .. k that is live (>= 0) and
-// has the row's ep_seq.  The ordinals load together (no load waits for a
-// compare); ep_seq does not decrease along an env's live steps, so the rows
-// of the episode are the run that ends at k.
-__device__ __forceinline__ int64_t stack_first(const OnlineView& ring, int64_t e, int64_t k, int n) {
-  if (n <= 1) return k;
-  int32_t seq[OGBX_VISUAL_MAX_STACK] = {};
-#pragma unroll
-  for (int i = 0; i < OGBX_VISUAL_MAX_STACK; ++i)
-    if (i < n && k - i >= 0) seq[i] = ring.ep_seq[phys_row(ring, e, k - i)];
-  int run = 0;  // rows before k that belong
-  bool open = true;
-#pragma unroll
-  for (int i = 1; i < OGBX_VISUAL_MAX_STACK; ++i) {
-    open = open && i < n && k - i >= 0 && seq[i] == seq[0];
-    run += open ? 1 : 0;
-  }
-  return k - run;
-}
-
 __global__ void __launch_bounds__(kVisThreads) online_visual_gather_kernel(OnVisArgs a, OnVisColumns cols) {
   extern __shared__ uint4 onvis_lds4[];  // 16-byte aligned
   uint8_t* lds = reinterpret_cast<uint8_t*>(onvis_lds4);

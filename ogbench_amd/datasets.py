@@ -29,7 +29,9 @@ Batched, device-side counterparts of impls/utils/datasets.py (hliuson/ogbench):
                include/ogbx_online_visual.h), for ``HGCReplayBuffer`` too;
                with a TRL ``agent_name`` the reference's TRL batch over the
                snapshot (``online_trl_sample_kernel``,
-               include/ogbx_online_trl.h).
+               include/ogbx_online_trl.h); ``sample_atc(batch_size, k)`` is
+               ATCDataset.sample over the snapshot
+               (``online_atc_sample_kernel``, include/ogbx_online_atc.h).
 
 Every sample is ONE launch of ``gc_sample_kernel`` (libogbx): index draw,
 trajectory-end lookup, hindsight goal relabel and the row gathers of every
@@ -52,7 +54,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib, _online_trl, _online_visual
+from . import _lib, _online_atc, _online_trl, _online_visual
 from ._online_visual import OnlineVisualColumn
 
 
@@ -2345,6 +2347,21 @@ class GCReplayBuffer(_SamplerHost, _BufferHost, Dataset):
     live ``p_aug`` and ``HGCReplayBuffer`` with a TRL agent name raise
     NotImplementedError at construction.  A buffer without a TRL agent name
     keeps its ``sample``, its single launch and its batches.
+
+    ATC pairs.  ``sample_atc(batch_size, k)`` returns what the reference's
+    ``ATCDataset.sample(batch_size, k)`` (datasets.py:401-464) returns over
+    the snapshot without its ``next_observations``: ``observations`` at
+    anchors drawn from valid(k) -- every live row whose offset + k stays
+    inside its episode -- and ``positive_observations`` k steps later, both
+    stacked and cropped from the ring's ``observations`` column by the
+    config's ``frame_stack`` / ``p_aug`` / ``augment_padding``.  valid(k) is
+    never built: an episode shorter than k + 1 holds no anchor, so the count
+    per env is a sum over its live episodes, which ``ogbx_online_atc_table``
+    walks once per ``(steps, clears, stream, k)``; the sample's one launch
+    turns a pick into a row by a search over the envs' prefix sum and one over
+    the env's episodes (include/ogbx_online_atc.h).  Its tables are allocated
+    by the first call: a buffer that never draws pairs holds none, and its
+    ``sample`` is untouched.  Every buffer class and config takes it.
     """
 
     RESERVED = ('masks', 'rewards', 'value_goals', 'actor_goals', 'valids')
@@ -2744,6 +2761,170 @@ class GCReplayBuffer(_SamplerHost, _BufferHost, Dataset):
             self._check_bad(bad, B, 'online_trl_sample')
         if record_draws:
             out.update(self._recorded(rec_t, idx_t, midpoint=mid_rec))
+        return out
+
+    # --------------------------------------------------------------- ATC batches
+    atc_table_builds = 0  # launches of the ATC table build so far (the first sample_atc makes it the instance's)
+    _atc_bad = None  # the device counter of sample_atc's unchecked calls, from its first call on
+
+    def _init_atc(self):
+        """What the first ``sample_atc`` allocates: the segment table ``W``,
+        the prefix table ``P``, the storage of the table build and the counter
+        of bad samples.  A buffer that never draws ATC pairs holds none."""
+        torch = _torch()
+        pad = int(self.config.get('augment_padding', ATC_CROP_PADDING))
+        if pad < 0:
+            raise ValueError(f'augment_padding must be >= 0, got {pad}')
+        L = _online_atc.bind()
+        need = ctypes.c_size_t(0)
+        _lib.check(L.ogbx_online_atc_table_bytes(self.num_envs, ctypes.byref(need)), 'online_atc_table_bytes')
+        self._atc_pad = pad
+        self._atc_W = torch.zeros(self.horizon, self.num_envs, dtype=torch.int32, device=self.device)
+        self._atc_P = torch.zeros(self.num_envs + 1, dtype=torch.int64, device=self.device)
+        self._atc_tmp = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        self._atc_bad = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._atc_built = None  # (steps, clears, stream, k) W and P were built for
+        self._atc_cache = {}
+        self._atc_gen = self._gen
+        self._La = L
+
+    def atc_bad_samples(self):
+        """Samples of ``sample_atc``'s Philox calls so far that found valid(k)
+        empty (one read of the device counter): nonzero only when every live
+        episode was shorter than k + 1 at the time of a call."""
+        return int(self._atc_bad.item()) if self._atc_bad is not None else 0
+
+    def _atc_batch(self, B):
+        """A new ATC batch: the output dict (the reference's key order) and
+        its column descriptor over the ring's ``observations``."""
+        torch = _torch()
+        src = self._column_of('observations', self.rows)
+        shape = tuple(src.shape[1:])
+        F = self._frame_stack or 1
+        oshape = (B,) + shape[:-1] + (shape[-1] * F,) if shape else (B,)
+        out = {k: torch.empty(oshape, dtype=src.dtype, device=self.device)
+               for k in ('observations', 'positive_observations')}
+        # an image is [H, W, C]; any other row is a 1-row image of its leading elements (ATCDataset._batch)
+        if len(shape) == 3:
+            H, W = shape[0], shape[1]
+        else:
+            H, W = 1, int(np.prod(shape[:-1], dtype=np.int64))
+        px = (shape[-1] if shape else 1) * src.element_size()
+        col = AtcColumn(src.data_ptr(), out['observations'].data_ptr(), out['positive_observations'].data_ptr(),
+                        H, W, px, int(src.dim() == 4))
+        return out, col
+
+    def sample_atc(self, batch_size, k, evaluation=False, idxs=None, draws=None, record_draws=False, out=None):
+        """ATCDataset.sample(batch_size, k) (datasets.py:401-415) over the
+        snapshot without its ``next_observations``: ``observations`` at the
+        anchors and ``positive_observations`` k steps later in the same
+        episode, both from the ``observations`` column, stacked by the
+        config's ``frame_stack`` as a visual ``sample`` stacks (an episode
+        whose head was overwritten starts at its oldest live row) and, when
+        the call's coin comes up (``p_aug``, GCDataset's rule), cropped with
+        one ``(cy, cx)`` per sample at padding ``augment_padding`` (default
+        4).  Every live row is a candidate.
+
+        valid(k) changes with every insert and is never built: the buffer
+        keeps ``W`` (per env, the anchors before each live episode) and ``P``
+        (their prefix sum over envs) and rebuilds both when ``steps``, the
+        count of ``clear()`` calls, the stream or ``k`` changed since the last
+        build (``ogbx_online_atc_table``; ``atc_table_builds`` counts), then
+        issues ONE launch of ``online_atc_sample_kernel``
+        (``ogbx_online_atc_sample``, include/ogbx_online_atc.h).  All of it is
+        allocated by the first call.
+
+        k: the temporal offset, an int >= 0; ``k >= live_steps`` raises the
+        reference's ValueError.  A valid(k) that is empty because every live
+        episode is shorter than k + 1 is not read back: the Philox path counts
+        its samples in ``atc_bad_samples()``.
+        idxs: explicit flat rows; those that leave the snapshot or whose
+        idx + k leaves their episode raise ValueError with their count (one
+        read-back).
+        draws: ``'pick'`` (positions into valid(k), snapshot order) and
+        ``'crop_from'`` ([batch_size, 2], used when the call crops).
+        record_draws: adds ``_idxs`` (flat rows) and ``_draws``.
+        out: a batch of an earlier plain call with the same batch_size,
+        refilled in place (stream ordered); k may differ between the calls.
+        Seeds and calls come from the buffer's one counter."""
+        torch = _torch()
+        B, k = int(batch_size), operator.index(k)
+        if k < 0:
+            raise ValueError(f'k must be >= 0, got {k}')
+        if self._steps == 0:
+            raise ValueError(f'cannot sample from an empty {self._NAME}')
+        if k >= self.live_steps:  # no episode holds k + 1 live rows
+            raise ValueError(f'No valid ATC indices found for k={k}.')
+        if self._atc_bad is None:
+            self._init_atc()
+        # the coin stays on the host (datasets.py:411-412); the offsets are device draws
+        crop = bool(self._p_aug_live and not evaluation and np.random.rand() < self._p_aug)
+        draws = dict(draws or {})
+        crop_from, pick = draws.pop('crop_from', None), draws.pop('pick', None)
+        if draws:
+            raise ValueError(f'unknown draw {sorted(draws)[0]!r}')
+        cf = pk = ix = None
+        if crop and crop_from is not None:
+            cf = self._stage_crop_from(crop_from, B)
+        if pick is not None:
+            pk = _to_device(pick, self.device).to(torch.int64).reshape(-1)
+            if pk.numel() != B:
+                raise ValueError(f"draw 'pick' must have {B} entries, got {pk.numel()}")
+        if idxs is not None:
+            ix = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
+            if ix.numel() != B:
+                raise ValueError(f'idxs must have {B} entries, got {ix.numel()}')
+        plain = ix is None and pk is None and crop_from is None and not record_draws
+        if self._atc_gen != self._gen:  # a column was replaced
+            self._atc_cache.clear()
+            self._atc_gen = self._gen
+        hit = self._atc_cache.get(id(out)) if (out is not None and plain) else None
+        if hit is not None and hit[0] is out and hit[1] == B:
+            col = hit[2]
+        else:
+            if out is not None and len(out['observations']) != B:
+                raise ValueError(f"out= holds a batch of {len(out['observations'])} samples, not {B}")
+            out, col = self._atc_batch(B)
+            if plain:
+                self._remember(self._atc_cache, out, B, col)
+        rec = {}
+        if record_draws:
+            rec = dict(idxs=torch.empty(B, dtype=torch.int64, device=self.device),
+                       pick=torch.empty(B, dtype=torch.int64, device=self.device))
+            if crop:
+                rec['crop_from'] = torch.empty((B, 2), dtype=torch.int64, device=self.device)
+        # explicit rows and injected picks have the kernel count their bad
+        # samples apart and read the count back (one sync); the Philox path
+        # counts into the buffer's counter and reads nothing back
+        checked = ix is not None or pk is not None
+        bad = torch.zeros(1, dtype=torch.int64, device=self.device) if checked else self._atc_bad
+        outs = AtcOutputs(_lib.ptr(rec.get('idxs')), _lib.ptr(rec.get('pick')), _lib.ptr(rec.get('crop_from')),
+                          bad.data_ptr())
+        seed, call = self._next_seed()
+        stream = self._raw_stream(self._dev_idx)
+        L = self._La
+        built = (self._steps, self._clears, stream, k)
+        if built != self._atc_built:
+            _lib.check(L.ogbx_online_atc_table(self._ring, k, self._atc_W.data_ptr(), self._atc_P.data_ptr(),
+                                               self._atc_tmp.data_ptr(), self._atc_tmp.numel(), stream),
+                       'online_atc_table')
+            self._atc_built = built
+            self.atc_table_builds += 1
+        _lib.check(L.ogbx_online_atc_sample(
+            self._ring, k, self._atc_W.data_ptr(), self._atc_P.data_ptr(), col, B, self._frame_stack or 1,
+            self._atc_pad, _lib.ptr(ix), _lib.ptr(pk), _lib.ptr(cf), int(crop and cf is None), seed, call, outs,
+            stream), 'online_atc_sample')
+        del cf, pk  # alive until the launch was issued
+        if checked:
+            nbad = int(bad.item())
+            if nbad and ix is not None:
+                raise ValueError(f'online_atc_sample: {nbad} of {B} samples have idx + k (k={k}) past the end of '
+                                 f'their episode, or idx outside the snapshot')
+            if nbad:
+                raise ValueError(f'No valid ATC indices found for k={k}.')
+        if record_draws:
+            out['_idxs'] = rec.pop('idxs')
+            out['_draws'] = rec
         return out
 
     # ------------------------------------- what HGCReplayBuffer supplies instead
