@@ -5,8 +5,9 @@
 // pinned to MuJoCo's published formulation by tests/mjmodel_np.py, not to
 // MuJoCo's output), with a short per-stage instruction stream.  The step
 // kernel runs one wave per SIMD and every wave that holds a contact lane runs
-// the whole 20-stage chain, so the launch time is the instruction count (and
-// dependency depth) of one stage x 20.
+// the whole chain of stages (20, of which the last has no solve: see below), so
+// the launch time is the instruction count (and dependency depth) of one stage
+// x 19.
 //
 //   * Solver.  The optimum u* of
 //       f(u) = 1/2 M |u - cu|^2 + sum_s sum_e 1/2 w_s c_e min(0, r_se)^2
@@ -32,6 +33,16 @@
 //     gains in closed form), both well inside the 1e-9 oracle tolerance, and
 //     the choice is per lane, so a lane's result never depends on which envs
 //     share its wavefront.
+//   * The last stage.  A step starts at rest and returns the position only;
+//     the velocity after the fifth substep is discarded.  A substep's position
+//     update uses its four stage velocities, and the fourth, v + h f(third
+//     stage), needs the third solve but not the fourth: the solve of the
+//     step's last stage (RK phase 3 of the last substep) reaches nothing.
+//     Both loops therefore end after the last stage's position offsets: no
+//     collision (the lean loop keeps the frame-validity word of its offsets),
+//     no solve, no active-set iterations and no safety net there.  Whether
+//     that stage's active set would have settled no longer decides which
+//     loop's result a lane keeps; the choice is still per lane.
 //
 // Contact flags and free-space steps are bit-identical to the oracle (same
 // closest-point arithmetic).
@@ -353,7 +364,8 @@ __device__ __forceinline__ uint32_t stage_contacts(const PointModel& pm, const u
 // stage's frame, contacts and collider choice the caller has computed: frame
 // refresh when the centre leaves its cell's half size, the generic collider
 // per lane, and the damped-Newton safety net.  Takes the lanes the lean loop
-// hands over (point_step_as).
+// hands over (point_step_as).  The step's last stage is its position update
+// only (header: the last stage).
 template <int kG = kMaxContacts>
 __device__ __forceinline__ void contact_loop(const PointModel& pm, const uint16_t* wall, int H, int W, double& x,
                                              double& y, RoleFrame fr, Contacts c, uint32_t valid, bool generic) {
@@ -376,7 +388,10 @@ __device__ __forceinline__ void contact_loop(const PointModel& pm, const uint16_
 #pragma unroll 4
   for (int e = 0; e < nstage; ++e) {
     const int st = e & 3;
-    if (e != 0) {
+    // the step's last stage (header: the last stage): no frame refresh, no
+    // collision, no solve -- only the position update it closes
+    const bool last = e + 1 == nstage;
+    if (e != 0 && !last) {
       const double lim = 0.5 * pm.unit;
       const bool stale = !(fabs(qsx - fr.cx) <= lim) | !(fabs(qsy - fr.cy) <= lim);
       if (__builtin_expect(__any(stale), 0)) {
@@ -384,8 +399,8 @@ __device__ __forceinline__ void contact_loop(const PointModel& pm, const uint16_
       }
       valid = stage_contacts<kG>(pm, wall, H, W, qsx, qsy, fr, c, &generic);
     }
-    double fx, fy;
-    {
+    double fx = 0.0, fy = 0.0;
+    if (!last) {
 #pragma clang fp contract(fast)
       double ux, uy;
       if (generic) solve_active_set<false, kG>(pm, c, valid, vsx, vsy, &act, pw, &ux, &uy);
@@ -449,8 +464,10 @@ __device__ __forceinline__ void contact_loop(const PointModel& pm, const uint16_
 // A lane bails to the full loop when its centre leaves the inner part of its
 // cell (e = h - X < 0) or crosses to the far side of its step-start half
 // (e >= h + 1.25, never reachable in a step: contacts move the centre by a
-// fraction of their penetration), or when its active set does not settle in
-// kLeanIters iterations.
+// fraction of their penetration), or when the active set of one of its 19
+// solved stages does not settle in kLeanIters iterations.  The step's last
+// stage has no solve (header: the last stage), so it cannot set the flag: a
+// lane whose last stage would not have settled keeps the lean result.
 struct LeanSides {
   double cx, cy, sxd, syd;
   // per-side radius: r where the side holds a wall, -1e3 where it does not
@@ -515,13 +532,15 @@ __device__ unsigned long long g_wave_paths[4096];
 #ifdef OGBX_MASK_TRACE
 // Diagnostic build only: per global thread (= env at 64 envs per wave) and
 // lean stage, the active-edge mask the stage started from and the one it
-// settled on (scripts/probe_mask_trace.py).
+// settled on (scripts/probe_mask_trace.py); the last stage, which has no
+// solve, writes the mask it carries as both words (scripts/probe_last_stage.py).
 __device__ uint32_t g_mask_trace[65536 * 40];
 #endif
 
 #ifdef OGBX_STAGE_STAMPS
 // Diagnostic build only: shader-clock cycles per part of the lean stage,
-// summed over the step's 20 stages, per wave (first active lane stores):
+// summed over the step's 20 stages (the last one is its RK offsets, part 0,
+// and nothing else), per wave (first active lane stores):
 // 0 RK offsets + next collision, 1 piece solve, 2 edge mask (+ the first
 // stage's Newton step), 3 next slots (band gains, weights), 4 active-set
 // iterations, 5 RK update; 6 iteration trips, 7 stages that iterated.  Each
@@ -667,12 +686,16 @@ __device__ __forceinline__ void local_slots(const PointModel& pm, const LeanHit&
 constexpr uint32_t kLeanEhiLimit = 0x400A0000u;  // high word of 3.25
 static_assert(kPointModel.box_hxy + 1.25 == 3.25, "kLeanEhiLimit is the high word of h + 1.25");
 
-__device__ __forceinline__ void local_collide(const LeanSides& L, double ex, double ey, LeanHit& k, uint32_t& ehi) {
-  k.ex = ex;
-  k.ey = ey;
+__device__ __forceinline__ void local_track(double ex, double ey, uint32_t& ehi) {
   // (asm: otherwise LLVM defers the max to the end of the step and keeps
   // every stage's e alive in registers)
   asm("v_max3_u32 %0, %1, %2, %3" : "=v"(ehi) : "v"(ehi), "v"(__double2hiint(ex)), "v"(__double2hiint(ey)));
+}
+
+__device__ __forceinline__ void local_collide(const LeanSides& L, double ex, double ey, LeanHit& k, uint32_t& ehi) {
+  k.ex = ex;
+  k.ey = ey;
+  local_track(ex, ey, ehi);
   k.d0 = ex - L.rX;
   k.d1 = ey - L.rY;
   const double d2 = fma(ex, ex, ey * ey);
@@ -721,11 +744,13 @@ __device__ __forceinline__ void contact_loop_local(const PointModel& pm, double&
   PieceWeights pw;
   piece_weights_from(ea, pw);
   const int nstage = 4 * pm.nsub;
+  // every stage but the step's last has a solve (header: the last stage)
+  const int nsolve = nstage - 1;
   OGBX_PS_AT(4);
 #pragma unroll 20
-  for (int e = 0; e < nstage; ++e) {
+  for (int e = 0; e < nsolve; ++e) {
     const int st = e & 3;
-    const bool more = e + 1 < nstage;
+    const bool more = e + 1 < nsolve;
     // the next stage's face offsets (velocities are carried divided by K, so
     // the position increment is (h K) cf vs; cf = 1/2 folds into the
     // constant exactly)
@@ -746,8 +771,11 @@ __device__ __forceinline__ void contact_loop_local(const PointModel& pm, double&
         ney = nEy;
       }
     }
+    // (the last stage has no solve and so no slots: of its collision only the
+    // frame-validity word)
     LeanHit k;
     if (more) local_collide(L, nex, ney, k, ehi);
+    else local_track(nex, ney, ehi);
     OGBX_SS_AT(ss0);
 #ifdef OGBX_MASK_TRACE
     const uint32_t mt_tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -864,6 +892,27 @@ __device__ __forceinline__ void contact_loop_local(const PointModel& pm, double&
     OGBX_SS_AT(ss5);
     if (e == 0) OGBX_PS_AT(5);
   }
+  // The last stage (RK phase 3 of the last substep): its offsets, which close
+  // the substep's position update, and nothing else.
+  {
+#pragma clang fp contract(fast)
+    const double nsqx = sqx + (1.0 / 6.0) * vsx;
+    const double nsqy = sqy + (1.0 / 6.0) * vsy;
+    Ex = fma(-kHK, nsqx, Ex);
+    Ey = fma(-kHK, nsqy, Ey);
+  }
+  OGBX_SS_AT(ss0);
+#ifdef OGBX_MASK_TRACE
+  {
+    // the carried mask as both words: the stage neither starts from a mask
+    // nor settles on one
+    const uint32_t mt_tid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (mt_tid < 65536) {
+      g_mask_trace[mt_tid * 40 + 2 * nsolve] = act;
+      g_mask_trace[mt_tid * 40 + 2 * nsolve + 1] = act;
+    }
+  }
+#endif
   OGBX_PS_AT(6);
 #ifdef OGBX_STAGE_STAMPS
   {

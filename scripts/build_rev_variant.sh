@@ -11,7 +11,7 @@ make -s -C ogbench_amd/csrc >/dev/null
 SRC=${SRC:-locomaze}
 d=build/rev_$name
 rm -rf $d && mkdir -p $d/ogbench_amd $d/include
-cp -r ogbench_amd/csrc $d/ogbench_amd/ && cp include/ogbx.h $d/include/
+cp -r ogbench_amd/csrc $d/ogbench_amd/ && cp include/*.h $d/include/
 for f in ${FILES:-point_contact.h}; do git show "$rev:ogbench_amd/csrc/$f" > $d/ogbench_amd/csrc/$f; done
 H=/opt/rocm/bin/hipcc
 F="-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -Wno-unused-function -Wno-unused-variable -Wno-bitwise-instead-of-logical"
