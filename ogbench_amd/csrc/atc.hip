@@ -13,12 +13,15 @@
 // and the call), map the pick to a row through the valid(k) table or the
 // periodic closed form, take row + k on the positive side, and stage and
 // compose their image with visual_tile.h, the code visual_gather_kernel runs.
+// What the kernel and ogbx_atc_sample share with the ring's (online_atc.hip)
+// is in atc_device.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 
 #include "../../include/ogbx_atc.h"
+#include "atc_device.h"
 #include "common.h"
 #include "gc_device.h"
 #include "visual_tile.h"
@@ -45,14 +48,8 @@ struct AtcArgs {
 __global__ void __launch_bounds__(kVisThreads) atc_sample_kernel(AtcArgs a) {
   extern __shared__ uint4 atc_lds4[];
   uint8_t* lds = reinterpret_cast<uint8_t*>(atc_lds4);
-  // consecutive workgroup ids go round-robin to the 8 XCDs: the anchor and the
-  // positive workgroup of a sample run on one XCD, so the frames they share
-  // (F - k of F when k < F) are read from HBM once into that XCD's L2
-  const int64_t b = blockIdx.x;
-  const int64_t x = b & 7, i = b >> 3;
-  const int64_t grp = i >> 1;
-  const int side = (int)(i & 1);  // 0 anchor, 1 positive
-  const int64_t s = grp * 8 + x;
+  int side;  // 0 anchor, 1 positive
+  const int64_t s = atc_sample_of_block(blockIdx.x, &side);
   if (s >= a.total) return;
   const int t = threadIdx.x;
   const int64_t R = a.num_rows;
@@ -86,6 +83,8 @@ __global__ void __launch_bounds__(kVisThreads) atc_sample_kernel(AtcArgs a) {
   const int64_t start = stack_start(a.traj_end, r, F);
 
   const int p = a.padding;
+  // the crop block and the lane-0 records stay written out in both ATC kernels: a
+  // helper moved this kernel's code or the other's (profiles/atc_device_refactor_isa.txt)
   int cy = p, cx = p;  // identity
   if (a.crop_from || a.draw) {
     int64_t oy, ox;
@@ -177,15 +176,10 @@ ogbx_status ogbx_atc_sample(const ogbx_gc_buffer* buf, const ogbx_atc_column* co
   const std::string who = "ogbx_atc_sample: ";
   OGBX_CHECK(buf && col, OGBX_EINVAL, who + "null argument");
   OGBX_CHECK(buf->num_rows > 0 && buf->traj_end, OGBX_EINVAL, who + "empty trajectory buffer");
-  OGBX_CHECK(col->src && col->anchor && col->positive, OGBX_EINVAL, who + "null column pointer");
-  OGBX_CHECK(col->height > 0 && col->width > 0 && col->px_bytes > 0, OGBX_EINVAL, who + "bad image shape");
-  OGBX_CHECK(total > 0, OGBX_EINVAL, who + "total must be > 0");
-  OGBX_CHECK(k >= 0, OGBX_EINVAL, who + "k must be >= 0");
-  OGBX_CHECK(frame_stack >= 1 && frame_stack <= OGBX_VISUAL_MAX_STACK, OGBX_EINVAL,
-             who + "frame_stack must be in 1..8");
-  OGBX_CHECK(padding >= 0 && padding < (1 << 20), OGBX_EINVAL, who + "padding must be >= 0");
-  const ogbx_atc_outputs o = out ? *out : ogbx_atc_outputs{};
-  OGBX_CHECK(!o.crop_from || crop_from || draw_crop, OGBX_EINVAL, who + "crop_from output without crop offsets");
+  const AtcCall c{col,       total,     k,    frame_stack, padding, idxs, pick,
+                  crop_from, draw_crop, seed, call_index,  out ? *out : ogbx_atc_outputs{}};
+  if (ogbx_status st = check_atc_call(who, c)) return st;
+  const ogbx_atc_outputs& o = c.out;
 
   AtcArgs a{};
   if (valid) {
@@ -200,14 +194,9 @@ ogbx_status ogbx_atc_sample(const ogbx_gc_buffer* buf, const ogbx_atc_column* co
   }
   OGBX_CHECK(idxs || a.num_valid > 0, OGBX_EINVAL, who + "valid(k) is empty");
 
-  const int64_t F = frame_stack;
-  const int64_t row_bytes = (int64_t)col->width * col->px_bytes, frame = row_bytes * col->height;
-  OGBX_CHECK(frame * F <= (1ll << 30), OGBX_EINVAL, who + "image too large");
-  const uint32_t lds = std::max<uint32_t>(16u, vis_lds_bytes(frame, F));
-  // at least one image row per staged frame
-  OGBX_CHECK((int64_t)((lds / (uint32_t)F) & ~15u) >= row_bytes, OGBX_EINVAL, who + "image row too wide to stage");
-  const int64_t blocks = ((total + 7) / 8) * 8 * 2;
-  OGBX_CHECK(blocks <= 0x7fffffffll, OGBX_EINVAL, who + "too many (sample, side) pairs for one launch");
+  uint32_t lds = 0;
+  int64_t blocks = 0;
+  if (ogbx_status st = atc_launch_shape(who, c, &lds, &blocks)) return st;
 
   int dev = 0;
   OGBX_HIP(hipGetDevice(&dev));
@@ -218,20 +207,7 @@ ogbx_status ogbx_atc_sample(const ogbx_gc_buffer* buf, const ogbx_atc_column* co
   a.traj_end = buf->traj_end;
   a.num_rows = buf->num_rows;
   a.valid = valid;
-  a.k = k;
-  a.idxs = idxs;
-  a.pick = pick;
-  a.crop_from = crop_from;
-  a.out = o;
-  a.col = *col;
-  a.frame_stack = frame_stack;
-  a.padding = padding;
-  a.draw = draw_crop != 0 && !crop_from;
-  seed_key(seed, kTagAtcSample, &a.k0, &a.k1);
-  a.call_lo = (uint32_t)call_index;
-  a.call_hi = (uint32_t)(call_index >> 32);
-  a.lds_bytes = lds;
-  a.total = total;
+  fill_atc_args(a, c, lds);
   hipLaunchKernelGGL(atc_sample_kernel, dim3((uint32_t)blocks), dim3(kVisThreads), lds, (hipStream_t)stream, a);
   OGBX_LAUNCHED("atc_sample_kernel");
   return OGBX_OK;

@@ -25,9 +25,10 @@
 // halving search over P for the env, the env's two ordinals, a binary search
 // over W for the segment, one ep_end load for the segment's first offset;
 // then stack_first at the side's offset (online_device.h) and compose_frames
-// (visual_tile.h), the code online_visual_gather_kernel runs.  The table and
-// the sample are separate launches: P crosses workgroups and XCDs, and the
-// kernel boundary is what makes it visible.
+// (visual_tile.h), the code online_visual_gather_kernel runs.  What the kernel
+// and ogbx_online_atc_sample share with the dataset's is in atc_device.h.  The
+// table and the sample are separate launches: P crosses workgroups and XCDs,
+// and the kernel boundary is what makes it visible.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +37,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/ogbx_online_atc.h"
+#include "atc_device.h"
 #include "common.h"
 #include "gc_device.h"
 #include "online_device.h"
@@ -115,12 +117,8 @@ __global__ void __launch_bounds__(kCountThreads) online_atc_count_kernel(OnlineV
   if (lane == 0) A[e] = run;
 }
 
-constexpr unsigned kTableThreads = 256, kTableItems = OGBX_ONLINE_ATC_TABLE_TILE / kTableThreads;
-static_assert(kTableThreads * kTableItems == OGBX_ONLINE_ATC_TABLE_TILE, "the scan's tile is the header's");
-using AtcScanConfig =
-    rocprim::scan_config<kTableThreads, kTableItems, rocprim::block_load_method::block_load_transpose,
-                         rocprim::block_store_method::block_store_transpose,
-                         rocprim::block_scan_algorithm::using_warp_scan>;
+static_assert(OGBX_ONLINE_ATC_TABLE_TILE % kTableScanThreads == 0, "whole items per thread");
+using AtcScanConfig = TableScanConfig<OGBX_ONLINE_ATC_TABLE_TILE>;
 
 static hipError_t table_scan(void* temp, size_t& temp_bytes, const int64_t* A, int64_t* P, int64_t n,
                              hipStream_t s) {
@@ -192,12 +190,8 @@ __device__ __forceinline__ void select_anchor(const OnlineAtcArgs& a, int64_t j,
 __global__ void __launch_bounds__(kVisThreads) online_atc_sample_kernel(OnlineAtcArgs a) {
   extern __shared__ uint4 onatc_lds4[];
   uint8_t* lds = reinterpret_cast<uint8_t*>(onatc_lds4);
-  // the anchor and the positive workgroup of a sample on one XCD: see atc_sample_kernel
-  const int64_t blk = blockIdx.x;
-  const int64_t x = blk & 7, i = blk >> 3;
-  const int64_t grp = i >> 1;
-  const int side = (int)(i & 1);  // 0 anchor, 1 positive
-  const int64_t s = grp * 8 + x;
+  int side;  // 0 anchor, 1 positive
+  const int64_t s = atc_sample_of_block(blockIdx.x, &side);
   if (s >= a.total) return;
   const int t = threadIdx.x;
   const OnlineView& ring = a.ring;
@@ -230,6 +224,8 @@ __global__ void __launch_bounds__(kVisThreads) online_atc_sample_kernel(OnlineAt
   const int64_t ofirst = stack_first(ring, e, os, F);
 
   const int p = a.padding;
+  // the crop block and the lane-0 records stay written out in both ATC kernels: a
+  // helper moved this kernel's code or the other's (profiles/atc_device_refactor_isa.txt)
   int cy = p, cx = p;  // identity
   if (a.crop_from || a.draw) {
     int64_t oy, ox;
@@ -312,24 +308,13 @@ ogbx_status ogbx_online_atc_sample(const ogbx_online_ring* ring, int64_t k, cons
   if (ogbx_status st = check_ring(ring, who)) return st;
   OGBX_CHECK(W && P && col, OGBX_EINVAL, who + "null argument");
   OGBX_CHECK(ring->steps >= 1, OGBX_EINVAL, who + "the ring is empty (steps must be >= 1)");
-  OGBX_CHECK(col->src && col->anchor && col->positive, OGBX_EINVAL, who + "null column pointer");
-  OGBX_CHECK(col->height > 0 && col->width > 0 && col->px_bytes > 0, OGBX_EINVAL, who + "bad image shape");
-  OGBX_CHECK(total > 0, OGBX_EINVAL, who + "total must be > 0");
-  OGBX_CHECK(k >= 0, OGBX_EINVAL, who + "k must be >= 0");
-  OGBX_CHECK(frame_stack >= 1 && frame_stack <= OGBX_VISUAL_MAX_STACK, OGBX_EINVAL,
-             who + "frame_stack must be in 1..8");
-  OGBX_CHECK(padding >= 0 && padding < (1 << 20), OGBX_EINVAL, who + "padding must be >= 0");
-  const ogbx_atc_outputs o = out ? *out : ogbx_atc_outputs{};
-  OGBX_CHECK(!o.crop_from || crop_from || draw_crop, OGBX_EINVAL, who + "crop_from output without crop offsets");
-
-  const int64_t F = frame_stack;
-  const int64_t row_bytes = (int64_t)col->width * col->px_bytes, frame = row_bytes * col->height;
-  OGBX_CHECK(frame * F <= (1ll << 30), OGBX_EINVAL, who + "image too large");
-  const uint32_t lds = std::max<uint32_t>(16u, vis_lds_bytes(frame, F));
-  // at least one image row per staged frame
-  OGBX_CHECK((int64_t)((lds / (uint32_t)F) & ~15u) >= row_bytes, OGBX_EINVAL, who + "image row too wide to stage");
-  const int64_t blocks = ((total + 7) / 8) * 8 * 2;
-  OGBX_CHECK(blocks <= 0x7fffffffll, OGBX_EINVAL, who + "too many (sample, side) pairs for one launch");
+  const AtcCall c{col,       total,     k,    frame_stack, padding, idxs, pick,
+                  crop_from, draw_crop, seed, call_index,  out ? *out : ogbx_atc_outputs{}};
+  if (ogbx_status st = check_atc_call(who, c)) return st;
+  const ogbx_atc_outputs& o = c.out;
+  uint32_t lds = 0;
+  int64_t blocks = 0;
+  if (ogbx_status st = atc_launch_shape(who, c, &lds, &blocks)) return st;
 
   int dev = 0;
   OGBX_HIP(hipGetDevice(&dev));
@@ -342,20 +327,7 @@ ogbx_status ogbx_online_atc_sample(const ogbx_online_ring* ring, int64_t k, cons
   a.W = W;
   a.P = P;
   while (((int64_t)1 << a.env_iters) < a.ring.n) ++a.env_iters;
-  a.k = k;
-  a.idxs = idxs;
-  a.pick = pick;
-  a.crop_from = crop_from;
-  a.out = o;
-  a.col = *col;
-  a.frame_stack = frame_stack;
-  a.padding = padding;
-  a.draw = draw_crop != 0 && !crop_from;
-  seed_key(seed, kTagAtcSample, &a.k0, &a.k1);
-  a.call_lo = (uint32_t)call_index;
-  a.call_hi = (uint32_t)(call_index >> 32);
-  a.lds_bytes = lds;
-  a.total = total;
+  fill_atc_args(a, c, lds);
   hipLaunchKernelGGL(online_atc_sample_kernel, dim3((uint32_t)blocks), dim3(kVisThreads), lds, (hipStream_t)stream,
                      a);
   OGBX_LAUNCHED("online_atc_sample_kernel");

@@ -10,6 +10,8 @@
 #include <algorithm>
 #include <string>
 
+#include <rocprim/device/device_scan_config.hpp>
+
 #include "../../include/ogbx_online.h"
 #include "../../include/ogbx_visual.h"
 #include "common.h"
@@ -109,6 +111,15 @@ __device__ __forceinline__ int64_t stack_first(const OnlineView& ring, int64_t e
 }
 
 // ---------------------------------------------------------------- host side
+// The device-wide scan that turns the per-env counts of a ring table into its
+// prefix table P (online_trl.hip, online_atc.hip), its tile fixed at Tile items.
+constexpr unsigned kTableScanThreads = 256;
+template <unsigned Tile>
+using TableScanConfig =
+    rocprim::scan_config<kTableScanThreads, Tile / kTableScanThreads, rocprim::block_load_method::block_load_transpose,
+                         rocprim::block_store_method::block_store_transpose,
+                         rocprim::block_scan_algorithm::using_warp_scan>;
+
 constexpr int64_t kOnlineMaxRows = (int64_t)1 << 46;  // flat indices stay exact in a double
 
 static ogbx_status check_ring(const ogbx_online_ring* r, const std::string& who) {

@@ -55,17 +55,13 @@ struct PickableRows {
   }
 };
 
-constexpr unsigned kTableThreads = 256, kTableItems = OGBX_ONLINE_TRL_TABLE_TILE / kTableThreads;
-static_assert(kTableThreads * kTableItems == OGBX_ONLINE_TRL_TABLE_TILE, "the scan's tile is the header's");
-using TableScanConfig =
-    rocprim::scan_config<kTableThreads, kTableItems, rocprim::block_load_method::block_load_transpose,
-                         rocprim::block_store_method::block_store_transpose,
-                         rocprim::block_scan_algorithm::using_warp_scan>;
+static_assert(OGBX_ONLINE_TRL_TABLE_TILE % kTableScanThreads == 0, "whole items per thread");
+using TrlScanConfig = TableScanConfig<OGBX_ONLINE_TRL_TABLE_TILE>;
 
 static hipError_t table_scan(void* temp, size_t& temp_bytes, const PickableRows& rows, int64_t* P, hipStream_t s) {
   auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<int64_t>(0), rows);
-  return rocprim::exclusive_scan<TableScanConfig>(temp, temp_bytes, in, P, (int64_t)0, (size_t)(rows.n + 1),
-                                                  rocprim::plus<int64_t>(), s);
+  return rocprim::exclusive_scan<TrlScanConfig>(temp, temp_bytes, in, P, (int64_t)0, (size_t)(rows.n + 1),
+                                                rocprim::plus<int64_t>(), s);
 }
 
 // ----------------------------------------------------------------- the select

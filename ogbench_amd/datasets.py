@@ -568,6 +568,21 @@ class _CallHost:
             cache.clear()
         cache[id(out)] = (out, shape, *held)
 
+    # Only an injected array comes through the two below: an out= refill has none.
+    def _stage_flat(self, v, total, what):
+        """An explicit array of ``total`` rows or draws as a flat int64 device tensor."""
+        t = _to_device(v, self.device).to(_torch().int64).reshape(-1)
+        if t.numel() != total:
+            raise ValueError(f'{what} must have {total} entries, got {t.numel()}')
+        return t
+
+    def _stage_crop_from(self, crop_from, total):
+        """Injected crop offsets as the [total, 2] int64 device tensor."""
+        cf = _to_device(crop_from, self.device).to(_torch().int64)
+        if tuple(cf.shape) != (total, 2):
+            raise ValueError(f"draws['crop_from'] must have shape ({total}, 2), got {tuple(cf.shape)}")
+        return cf
+
 
 class _SamplerHost(_CallHost):
     """The host side of goal-conditioned sampling that the dataset samplers
@@ -614,9 +629,7 @@ class _SamplerHost(_CallHost):
         if idxs is not None or draws:
             dr, gdr = self._draw_structs()
             if idxs is not None:
-                t = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
-                if t.numel() != total:
-                    raise ValueError(f'idxs must have {total} entries, got {t.numel()}')
+                t = self._stage_flat(idxs, total, 'idxs')
                 staged.append(t)
                 gdr.idxs = t.data_ptr()
             for k, v in (draws or {}).items():
@@ -640,20 +653,11 @@ class _SamplerHost(_CallHost):
     # The crop coin (datasets.py:278-279: one np.random.rand() on the host; the
     # offsets are device draws), the pops of 'crop_from' / 'midpoint' and the
     # *checked* rule of a TRL call stand in line in each visual and TRL
-    # sample(): an out= refill passes them.  Only an injected draw comes here.
-    def _stage_crop_from(self, crop_from, total):
-        """Injected crop offsets as the [total, 2] int64 device tensor."""
-        cf = _to_device(crop_from, self.device).to(_torch().int64)
-        if tuple(cf.shape) != (total, 2):
-            raise ValueError(f"draws['crop_from'] must have shape ({total}, 2), got {tuple(cf.shape)}")
-        return cf
-
+    # sample(): an out= refill passes them.  Only an injected draw is staged
+    # (``_CallHost._stage_crop_from``, and the midpoint here).
     def _stage_midpoint(self, midpoint, total):
         """Injected midpoint rows as an int64 device tensor of ``total``."""
-        mid_in = _to_device(midpoint, self.device).to(_torch().int64).reshape(-1)
-        if mid_in.numel() != total:
-            raise ValueError(f"draws['midpoint'] must have {total} entries, got {mid_in.numel()}")
-        return mid_in
+        return self._stage_flat(midpoint, total, "draws['midpoint']")
 
     @staticmethod
     def _check_bad(bad, total, what):
@@ -1596,7 +1600,96 @@ class HGCDataset(_HgcHost, GCDataset):
 # ----------------------------------------------------------------------------- ATCDataset
 
 
-class ATCDataset:
+class _AtcHost(_CallHost):
+    """The host side that ``ATCDataset.sample`` and ``GCReplayBuffer.sample_atc``
+    share: the batch layout and, in ``_atc_call``, every call that is not a
+    steady ``out=`` refill (staging, the plain rule, the ``out=`` cache, the
+    record tensors, the seed, the bad-sample readback, the ``_*`` keys).  The
+    refill stays in line in both sample methods (``_CallHost._remember``): the
+    ``k`` check, the family's staleness and empty tests, the coin, the lookup
+    and on a hit the one ctypes call, so that it makes no Python call the
+    written-out methods did not (profiles/atc_host_refactor_ab.txt).  A family
+    supplies ``device``, ``_frame_stack``, ``_atc_cache``, ``_atc_source`` (its
+    observations), ``_atc_launch`` (its entry point) and what follows."""
+
+    _atc_out_strict = False  # an out= of another batch size raises ValueError (ATCDataset: builds a new batch)
+    _atc_pick_checked = False  # an injected pick makes the call read its bad count back (the ring's empty valid(k))
+    _atc_bad = None  # where an unchecked call counts its bad samples (the ring's device counter)
+    _atc_bad_rows = None  # the family's message for bad explicit rows, over n, B and k
+
+    def _atc_layout(self, src, B):
+        """A new batch over the observations ``src``: the output dict (the
+        reference's key order) and its column descriptor."""
+        torch = _torch()
+        shape = tuple(src.shape[1:])
+        F = self._frame_stack or 1
+        oshape = (B,) + shape[:-1] + (shape[-1] * F,) if shape else (B,)
+        out = {k: torch.empty(oshape, dtype=src.dtype, device=self.device)
+               for k in ('observations', 'positive_observations')}
+        # an image is [H, W, C]; any other row is a 1-row image of its leading elements
+        if len(shape) == 3:
+            H, W = shape[0], shape[1]
+        else:
+            H, W = 1, int(np.prod(shape[:-1], dtype=np.int64))
+        px = (shape[-1] if shape else 1) * src.element_size()
+        col = AtcColumn(src.data_ptr(), out['observations'].data_ptr(), out['positive_observations'].data_ptr(),
+                        H, W, px, int(src.dim() == 4))
+        return out, col
+
+    def _atc_call(self, B, k, crop, idxs, draws, record_draws, out, table):
+        """Every call but the in-line refill: ``crop`` is the coin's answer,
+        ``table`` what the family's ``_atc_launch`` takes first."""
+        torch = _torch()
+        draws = dict(draws or {})
+        crop_from, pick = draws.pop('crop_from', None), draws.pop('pick', None)
+        if draws:
+            raise ValueError(f'unknown draw {sorted(draws)[0]!r}')
+        cf = pk = ix = None
+        if crop and crop_from is not None:
+            cf = self._stage_crop_from(crop_from, B)
+        if pick is not None:
+            pk = self._stage_flat(pick, B, "draw 'pick'")
+        if idxs is not None:
+            ix = self._stage_flat(idxs, B, 'idxs')
+        plain = ix is None and pk is None and crop_from is None and not record_draws
+        hit = self._atc_cache.get(id(out)) if (out is not None and plain) else None
+        fresh = hit is None or hit[0] is not out or hit[1] != B
+        if not fresh:  # a refill whose draws held only None
+            col = hit[2]
+        else:
+            if self._atc_out_strict and out is not None and len(out['observations']) != B:
+                raise ValueError(f"out= holds a batch of {len(out['observations'])} samples, not {B}")
+            out, col = self._atc_layout(self._atc_source(), B)
+        rec = {}
+        if record_draws:
+            rec = dict(idxs=torch.empty(B, dtype=torch.int64, device=self.device),
+                       pick=torch.empty(B, dtype=torch.int64, device=self.device))
+            if crop:
+                rec['crop_from'] = torch.empty((B, 2), dtype=torch.int64, device=self.device)
+        # explicit rows (over the ring, injected picks too) are counted apart and the count
+        # is read back (one sync); the Philox path counts into the family's counter, if any
+        checked = ix is not None or (pk is not None and self._atc_pick_checked)
+        bad = torch.zeros(1, dtype=torch.int64, device=self.device) if checked else self._atc_bad
+        outs = AtcOutputs(_lib.ptr(rec.get('idxs')), _lib.ptr(rec.get('pick')), _lib.ptr(rec.get('crop_from')),
+                          _lib.ptr(bad))
+        if plain and fresh:
+            self._remember(self._atc_cache, out, B, col, outs)  # what a refill passes on
+        seed, call = self._next_seed()
+        self._atc_launch(table, col, B, k, ix, pk, cf, int(crop and cf is None), seed, call, outs)
+        del cf, pk  # alive until the launch was issued
+        if checked:
+            nbad = int(bad.item())
+            if nbad and ix is not None:
+                raise ValueError(self._atc_bad_rows.format(n=nbad, B=B, k=k))
+            if nbad:
+                raise ValueError(f'No valid ATC indices found for k={k}.')
+        if record_draws:
+            out['_idxs'] = rec.pop('idxs')
+            out['_draws'] = rec
+        return out
+
+
+class ATCDataset(_AtcHost):
     """Anchor / positive observation pairs for ATC pretraining (reference:
     datasets.py:369-464; consumed by impls/pretrain_atc.py:167-251).
 
@@ -1689,11 +1782,9 @@ class ATCDataset:
         self._tables = {}  # k -> (valid(k) or None, its size), least recently used first
         self._seed = int(seed) if seed is not None else None
         self._calls = 0
-        self._out_cache = {}
+        self._atc_cache = {}
         self._tok_ds, self._tok_gen = dataset, dataset._gen
         self._obs = dataset['observations']
-
-    _next_seed = GCDataset._next_seed
 
     # ---------------------------------------------------------------- valid(k)
     def _valid_k(self, k):
@@ -1729,28 +1820,24 @@ class ATCDataset:
             raise ValueError("dataset column 'observations' changed shape, dtype or device after the sampler was "
                              'built')
         self._obs = obs
-        self._out_cache.clear()
+        self._atc_cache.clear()
         self._tok_ds, self._tok_gen = ds, ds._gen
 
+    # ------------------------------------------------- what _AtcHost asks for
+    _atc_bad_rows = ('atc_sample: {n} of {B} samples have idx + k (k={k}) past the end of their trajectory, or idx '
+                     'outside the dataset')
+
+    def _atc_source(self):
+        return self._obs
+
     def _batch(self, B):
-        """A new batch: the output dict (the reference's key order) and its
-        column descriptor."""
-        torch = _torch()
-        src = self._obs
-        shape = tuple(src.shape[1:])
-        F = self._frame_stack or 1
-        oshape = (B,) + shape[:-1] + (shape[-1] * F,) if shape else (B,)
-        out = {k: torch.empty(oshape, dtype=src.dtype, device=self.device)
-               for k in ('observations', 'positive_observations')}
-        # an image is [H, W, C]; any other row is a 1-row image of its leading elements
-        if len(shape) == 3:
-            H, W = shape[0], shape[1]
-        else:
-            H, W = 1, int(np.prod(shape[:-1], dtype=np.int64))
-        px = (shape[-1] if shape else 1) * src.element_size()
-        col = AtcColumn(src.data_ptr(), out['observations'].data_ptr(), out['positive_observations'].data_ptr(),
-                        H, W, px, int(src.dim() == 4))
-        return out, col
+        """A new batch over the dataset's observations (tests build their column through it)."""
+        return self._atc_layout(self._obs, B)
+
+    def _atc_launch(self, valid, col, B, k, ix, pk, cf, draw, seed, call, outs):
+        _lib.check(self._L.ogbx_atc_sample(
+            self._buf, col, B, k, _lib.ptr(valid[0]), valid[1], self._frame_stack or 1, self._padding, _lib.ptr(ix),
+            _lib.ptr(pk), _lib.ptr(cf), draw, seed, call, outs, _lib.stream_of(self.device)), 'atc_sample')
 
     def sample(self, batch_size, k, evaluation=False, idxs=None, draws=None, record_draws=False, out=None):
         """ATCDataset.sample (datasets.py:401-415), one launch.
@@ -1767,70 +1854,26 @@ class ATCDataset:
         no idxs / draws / record_draws): refilled in place, stream ordered,
         and returned.
         """
-        torch = _torch()
         B, k = int(batch_size), operator.index(k)
         if k < 0:
             raise ValueError(f'k must be >= 0, got {k}')
         ds = self.dataset
         if ds is not self._tok_ds or getattr(ds, '_gen', None) != self._tok_gen:
             self._refresh()
-        table, n = self._valid_k(k)
-        if n == 0:
+        valid = self._valid_k(k)
+        if valid[1] == 0:
             raise ValueError(f'No valid ATC indices found for k={k}.')
         # the coin stays on the host (datasets.py:411-412); the offsets are device draws
         crop = bool(self._p_aug_live and not evaluation and np.random.rand() < self._p_aug)
-        draws = dict(draws or {})
-        crop_from, pick = draws.pop('crop_from', None), draws.pop('pick', None)
-        if draws:
-            raise ValueError(f'unknown draws {sorted(draws)}')
-        cf = pk = ix = None
-        if crop and crop_from is not None:
-            cf = _to_device(crop_from, self.device).to(torch.int64)
-            if tuple(cf.shape) != (B, 2):
-                raise ValueError(f"draws['crop_from'] must have shape ({B}, 2), got {tuple(cf.shape)}")
-        if pick is not None:
-            pk = _to_device(pick, self.device).to(torch.int64).reshape(-1)
-            if pk.numel() != B:
-                raise ValueError(f"draws['pick'] must have {B} entries, got {pk.numel()}")
-        if idxs is not None:
-            ix = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
-            if ix.numel() != B:
-                raise ValueError(f'idxs must have {B} entries, got {ix.numel()}')
-        plain_call = ix is None and pk is None and crop_from is None and not record_draws
-        hit = self._out_cache.get(id(out)) if (out is not None and plain_call) else None
-        if hit is not None and hit[0] is out and hit[1] == B:
-            col = hit[2]
-        else:
-            out, col = self._batch(B)
-            if plain_call:
-                if len(self._out_cache) >= 2:
-                    self._out_cache.clear()
-                self._out_cache[id(out)] = (out, B, col)
-        rec = {}
-        if record_draws:
-            rec = dict(idxs=torch.empty(B, dtype=torch.int64, device=self.device),
-                       pick=torch.empty(B, dtype=torch.int64, device=self.device))
-            if crop:
-                rec['crop_from'] = torch.empty((B, 2), dtype=torch.int64, device=self.device)
-        # explicit rows may leave their trajectory: such a call has the kernel
-        # count them and reads the count back (one sync); picks cannot
-        bad = torch.zeros(1, dtype=torch.int64, device=self.device) if ix is not None else None
-        outs = AtcOutputs(_lib.ptr(rec.get('idxs')), _lib.ptr(rec.get('pick')), _lib.ptr(rec.get('crop_from')),
-                          _lib.ptr(bad))
+        # the conservative form of _atc_call's plain rule: a draws dict that holds only None goes there
+        plain = idxs is None and not draws and not record_draws
+        hit = self._atc_cache.get(id(out)) if (out is not None and plain) else None
+        if hit is None or hit[0] is not out or hit[1] != B:
+            return self._atc_call(B, k, crop, idxs, draws, record_draws, out, valid)
         seed, call = self._next_seed()
         _lib.check(self._L.ogbx_atc_sample(
-            self._buf, col, B, k, _lib.ptr(table), n, self._frame_stack or 1, self._padding, _lib.ptr(ix),
-            _lib.ptr(pk), _lib.ptr(cf), int(crop and cf is None), seed, call, outs,
-            _lib.stream_of(self.device)), 'atc_sample')
-        del cf, pk  # alive until the launch was issued
-        if bad is not None:
-            nbad = int(bad.item())
-            if nbad:
-                raise ValueError(f'atc_sample: {nbad} of {B} samples have idx + k (k={k}) past the end of their '
-                                 f'trajectory, or idx outside the dataset')
-        if record_draws:
-            out['_idxs'] = rec.pop('idxs')
-            out['_draws'] = rec
+            self._buf, hit[2], B, k, _lib.ptr(valid[0]), valid[1], self._frame_stack or 1, self._padding, None, None,
+            None, int(crop), seed, call, hit[3], _lib.stream_of(self.device)), 'atc_sample')
         return out
 
 
@@ -2244,7 +2287,7 @@ class ReplayBuffer(_BufferHost, Dataset):
         return self.sample(num_idxs, record_idxs=True)['_idxs']
 
 
-class GCReplayBuffer(_SamplerHost, _BufferHost, Dataset):
+class GCReplayBuffer(_SamplerHost, _AtcHost, _BufferHost, Dataset):
     """Hindsight goal sampling over an on-device episode ring: what batched
     envs produce, one row per env and step, sampled as the reference's
     ``GCDataset.sample`` (datasets.py:213-327) samples a dataset
@@ -2765,7 +2808,7 @@ class GCReplayBuffer(_SamplerHost, _BufferHost, Dataset):
 
     # --------------------------------------------------------------- ATC batches
     atc_table_builds = 0  # launches of the ATC table build so far (the first sample_atc makes it the instance's)
-    _atc_bad = None  # the device counter of sample_atc's unchecked calls, from its first call on
+    # _atc_bad: the device counter of sample_atc's unchecked calls, from its first call on
 
     def _init_atc(self):
         """What the first ``sample_atc`` allocates: the segment table ``W``,
@@ -2782,6 +2825,7 @@ class GCReplayBuffer(_SamplerHost, _BufferHost, Dataset):
         self._atc_W = torch.zeros(self.horizon, self.num_envs, dtype=torch.int32, device=self.device)
         self._atc_P = torch.zeros(self.num_envs + 1, dtype=torch.int64, device=self.device)
         self._atc_tmp = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        # allocated once and never replaced: the out= cache holds its address (the refill's AtcOutputs)
         self._atc_bad = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._atc_built = None  # (steps, clears, stream, k) W and P were built for
         self._atc_cache = {}
@@ -2794,25 +2838,31 @@ class GCReplayBuffer(_SamplerHost, _BufferHost, Dataset):
         episode was shorter than k + 1 at the time of a call."""
         return int(self._atc_bad.item()) if self._atc_bad is not None else 0
 
-    def _atc_batch(self, B):
-        """A new ATC batch: the output dict (the reference's key order) and
-        its column descriptor over the ring's ``observations``."""
-        torch = _torch()
-        src = self._column_of('observations', self.rows)
-        shape = tuple(src.shape[1:])
-        F = self._frame_stack or 1
-        oshape = (B,) + shape[:-1] + (shape[-1] * F,) if shape else (B,)
-        out = {k: torch.empty(oshape, dtype=src.dtype, device=self.device)
-               for k in ('observations', 'positive_observations')}
-        # an image is [H, W, C]; any other row is a 1-row image of its leading elements (ATCDataset._batch)
-        if len(shape) == 3:
-            H, W = shape[0], shape[1]
-        else:
-            H, W = 1, int(np.prod(shape[:-1], dtype=np.int64))
-        px = (shape[-1] if shape else 1) * src.element_size()
-        col = AtcColumn(src.data_ptr(), out['observations'].data_ptr(), out['positive_observations'].data_ptr(),
-                        H, W, px, int(src.dim() == 4))
-        return out, col
+    # what _AtcHost asks for
+    _atc_out_strict = True
+    _atc_pick_checked = True
+    _atc_bad_rows = ('online_atc_sample: {n} of {B} samples have idx + k (k={k}) past the end of their episode, or '
+                     'idx outside the snapshot')
+
+    def _atc_source(self):
+        return self._column_of('observations', self.rows)
+
+    def _atc_build(self, k, stream, built):
+        """W and P of valid(k) for ``built`` = (steps, clears, stream, k)."""
+        _lib.check(self._La.ogbx_online_atc_table(self._ring, k, self._atc_W.data_ptr(), self._atc_P.data_ptr(),
+                                                  self._atc_tmp.data_ptr(), self._atc_tmp.numel(), stream),
+                   'online_atc_table')
+        self._atc_built = built
+        self.atc_table_builds += 1
+
+    def _atc_launch(self, stream, col, B, k, ix, pk, cf, draw, seed, call, outs):
+        built = (self._steps, self._clears, stream, k)
+        if built != self._atc_built:
+            self._atc_build(k, stream, built)
+        _lib.check(self._La.ogbx_online_atc_sample(
+            self._ring, k, self._atc_W.data_ptr(), self._atc_P.data_ptr(), col, B, self._frame_stack or 1,
+            self._atc_pad, _lib.ptr(ix), _lib.ptr(pk), _lib.ptr(cf), draw, seed, call, outs, stream),
+            'online_atc_sample')
 
     def sample_atc(self, batch_size, k, evaluation=False, idxs=None, draws=None, record_draws=False, out=None):
         """ATCDataset.sample(batch_size, k) (datasets.py:401-415) over the
@@ -2847,7 +2897,6 @@ class GCReplayBuffer(_SamplerHost, _BufferHost, Dataset):
         out: a batch of an earlier plain call with the same batch_size,
         refilled in place (stream ordered); k may differ between the calls.
         Seeds and calls come from the buffer's one counter."""
-        torch = _torch()
         B, k = int(batch_size), operator.index(k)
         if k < 0:
             raise ValueError(f'k must be >= 0, got {k}')
@@ -2859,72 +2908,22 @@ class GCReplayBuffer(_SamplerHost, _BufferHost, Dataset):
             self._init_atc()
         # the coin stays on the host (datasets.py:411-412); the offsets are device draws
         crop = bool(self._p_aug_live and not evaluation and np.random.rand() < self._p_aug)
-        draws = dict(draws or {})
-        crop_from, pick = draws.pop('crop_from', None), draws.pop('pick', None)
-        if draws:
-            raise ValueError(f'unknown draw {sorted(draws)[0]!r}')
-        cf = pk = ix = None
-        if crop and crop_from is not None:
-            cf = self._stage_crop_from(crop_from, B)
-        if pick is not None:
-            pk = _to_device(pick, self.device).to(torch.int64).reshape(-1)
-            if pk.numel() != B:
-                raise ValueError(f"draw 'pick' must have {B} entries, got {pk.numel()}")
-        if idxs is not None:
-            ix = _to_device(idxs, self.device).to(torch.int64).reshape(-1)
-            if ix.numel() != B:
-                raise ValueError(f'idxs must have {B} entries, got {ix.numel()}')
-        plain = ix is None and pk is None and crop_from is None and not record_draws
         if self._atc_gen != self._gen:  # a column was replaced
             self._atc_cache.clear()
             self._atc_gen = self._gen
+        # the conservative form of _atc_call's plain rule: a draws dict that holds only None goes there
+        plain = idxs is None and not draws and not record_draws
         hit = self._atc_cache.get(id(out)) if (out is not None and plain) else None
-        if hit is not None and hit[0] is out and hit[1] == B:
-            col = hit[2]
-        else:
-            if out is not None and len(out['observations']) != B:
-                raise ValueError(f"out= holds a batch of {len(out['observations'])} samples, not {B}")
-            out, col = self._atc_batch(B)
-            if plain:
-                self._remember(self._atc_cache, out, B, col)
-        rec = {}
-        if record_draws:
-            rec = dict(idxs=torch.empty(B, dtype=torch.int64, device=self.device),
-                       pick=torch.empty(B, dtype=torch.int64, device=self.device))
-            if crop:
-                rec['crop_from'] = torch.empty((B, 2), dtype=torch.int64, device=self.device)
-        # explicit rows and injected picks have the kernel count their bad
-        # samples apart and read the count back (one sync); the Philox path
-        # counts into the buffer's counter and reads nothing back
-        checked = ix is not None or pk is not None
-        bad = torch.zeros(1, dtype=torch.int64, device=self.device) if checked else self._atc_bad
-        outs = AtcOutputs(_lib.ptr(rec.get('idxs')), _lib.ptr(rec.get('pick')), _lib.ptr(rec.get('crop_from')),
-                          bad.data_ptr())
-        seed, call = self._next_seed()
         stream = self._raw_stream(self._dev_idx)
-        L = self._La
+        if hit is None or hit[0] is not out or hit[1] != B:
+            return self._atc_call(B, k, crop, idxs, draws, record_draws, out, stream)
+        seed, call = self._next_seed()
         built = (self._steps, self._clears, stream, k)
         if built != self._atc_built:
-            _lib.check(L.ogbx_online_atc_table(self._ring, k, self._atc_W.data_ptr(), self._atc_P.data_ptr(),
-                                               self._atc_tmp.data_ptr(), self._atc_tmp.numel(), stream),
-                       'online_atc_table')
-            self._atc_built = built
-            self.atc_table_builds += 1
-        _lib.check(L.ogbx_online_atc_sample(
-            self._ring, k, self._atc_W.data_ptr(), self._atc_P.data_ptr(), col, B, self._frame_stack or 1,
-            self._atc_pad, _lib.ptr(ix), _lib.ptr(pk), _lib.ptr(cf), int(crop and cf is None), seed, call, outs,
-            stream), 'online_atc_sample')
-        del cf, pk  # alive until the launch was issued
-        if checked:
-            nbad = int(bad.item())
-            if nbad and ix is not None:
-                raise ValueError(f'online_atc_sample: {nbad} of {B} samples have idx + k (k={k}) past the end of '
-                                 f'their episode, or idx outside the snapshot')
-            if nbad:
-                raise ValueError(f'No valid ATC indices found for k={k}.')
-        if record_draws:
-            out['_idxs'] = rec.pop('idxs')
-            out['_draws'] = rec
+            self._atc_build(k, stream, built)
+        _lib.check(self._La.ogbx_online_atc_sample(
+            self._ring, k, self._atc_W.data_ptr(), self._atc_P.data_ptr(), hit[2], B, self._frame_stack or 1,
+            self._atc_pad, None, None, None, int(crop), seed, call, hit[3], stream), 'online_atc_sample')
         return out
 
     # ------------------------------------- what HGCReplayBuffer supplies instead

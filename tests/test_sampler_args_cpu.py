@@ -1,8 +1,8 @@
 """CPU: the argument rejects that the dataset and ring samplers word alike --
 ogbx_visual_gather / ogbx_online_visual_gather, ogbx_trl_sample /
-ogbx_online_trl_sample and the config and output checks of
-ogbx_online_hgc_sample against ogbx_hgc_sample -- driven through ctypes on
-libogbx.so.
+ogbx_online_trl_sample, ogbx_atc_sample / ogbx_online_atc_sample and the config
+and output checks of ogbx_online_hgc_sample against ogbx_hgc_sample -- driven
+through ctypes on libogbx.so.
 
 The pattern of test_gc_args_cpu.py and test_buffer_args_cpu.py: every case
 starts from an argument set the entry point would accept, violates what its id
@@ -19,13 +19,14 @@ import types
 
 import pytest
 
-from ogbench_amd import _lib, _online_trl, _online_visual
+from ogbench_amd import _lib, _online_atc, _online_trl, _online_visual
 from ogbench_amd import datasets as D
 
 VIS, RING_VIS = 'ogbx_visual_gather', 'ogbx_online_visual_gather'
 TRL, RING_TRL = 'ogbx_trl_sample', 'ogbx_online_trl_sample'
 HGC, RING_HGC = 'ogbx_hgc_sample', 'ogbx_online_hgc_sample'
-GATHERS, TRLS = (VIS, RING_VIS), (TRL, RING_TRL)
+ATC, RING_ATC = 'ogbx_atc_sample', 'ogbx_online_atc_sample'
+GATHERS, TRLS, ATCS = (VIS, RING_VIS), (TRL, RING_TRL), (ATC, RING_ATC)
 
 _HOST = (ctypes.c_double * 64)()  # stands in for every device buffer; never read or written
 ADDR = ctypes.addressof(_HOST)
@@ -51,11 +52,20 @@ def good():
     a.crop_from, a.draw_crop, a.crop_out = None, 1, ADDR
     a.P = ADDR
     a.record = D.GcDrawRecord(*[ADDR] * 11)
+    # the ATC pair: an image column that crops, a valid(2) table of 5 rows, every output asked for
+    a.atc = D.AtcColumn(ADDR, ADDR, ADDR, 8, 8, 3, 1)
+    a.aout = D.AtcOutputs(ADDR, ADDR, ADDR, ADDR)
+    a.k, a.valid, a.num_valid, a.W = 2, ADDR, 5, ADDR
     return a
 
 
 def call(who, a):
     L = D._bind_hgc()
+    if who in ATCS:
+        rest = (a.frame_stack, a.padding, None, None, a.crop_from, a.draw_crop, 1, 0, a.aout, None)
+        if who == ATC:
+            return L.ogbx_atc_sample(a.buf, a.atc, a.total, a.k, a.valid, a.num_valid, *rest)
+        return _online_atc.bind().ogbx_online_atc_sample(a.ring, a.k, a.W, a.P, a.atc, a.total, *rest)
     if who in GATHERS:
         hcfg = a.hcfg if a.use_hcfg else None
         colv = a.vis if who == VIS else a.rvis
@@ -126,6 +136,8 @@ SHAPE, STACK = 'bad image shape', 'frame_stack must be in 1..8'
 RECORD, SCALAR, TABLES = 'incomplete draw record', 'missing scalar output', 'missing reward/mask tables'
 VALUE_GOALS = 'a TRL batch needs value_p_curgoal == 0 and no random value goals (value_traj_thresh >= 1)'
 
+ATC_TOO_LARGE = both(setter('atc.height', 32768), setter('atc.width', 32768), setter('atc.px_bytes', 2))
+
 # (id, entry points, mutation, message after "<entry point>: ")
 CASES = (
     # ---- the two image gathers
@@ -187,6 +199,23 @@ CASES = (
         both(setter('hout.masks', None), setter('hcfg.low_subgoal_steps', 0)), 'subgoal steps must be >= 1'),
        ('low_discount_against_outputs', (RING_HGC,), both(setter('hout.rewards', None), setter('hcfg.low_discount', 1.0)),
         'low_discount must be in (0, 1)')]
+    # ---- the two ATC samplers
+    + [(f'atc_null_{k}', ATCS, setter(f'atc.{k}', None), 'null column pointer') for k in ('src', 'anchor', 'positive')]
+    + [(f'atc_{k}_0', ATCS, setter(f'atc.{k}', 0), SHAPE) for k in ('height', 'width', 'px_bytes')]
+    + [('atc_total_0', ATCS, setter('total', 0), 'total must be > 0'),
+       ('atc_k_negative', ATCS, setter('k', -1), 'k must be >= 0'),
+       ('atc_frame_stack_0', ATCS, setter('frame_stack', 0), STACK),
+       ('atc_frame_stack_9', ATCS, setter('frame_stack', 9), STACK),
+       ('atc_padding_negative', ATCS, setter('padding', -1), 'padding must be >= 0'),
+       ('atc_crop_from_output_without_offsets', ATCS, setter('draw_crop', 0), 'crop_from output without crop offsets'),
+       ('atc_image_too_large', ATCS, ATC_TOO_LARGE, 'image too large'),
+       ('atc_row_too_wide', ATCS, both(setter('atc.height', 1), setter('atc.width', 70000), setter('atc.px_bytes', 1),
+                                       setter('frame_stack', 1)), 'image row too wide to stage'),
+       ('atc_too_many_pairs', ATCS, setter('total', 1 << 31), 'too many (sample, side) pairs for one launch'),
+       # two faults: the order of the shared checks, and ogbx_atc_sample's valid(k) checks between its two blocks
+       ('atc_total_against_k', ATCS, both(setter('total', 0), setter('k', -1)), 'total must be > 0'),
+       ('atc_padding_against_too_large', ATCS, both(setter('padding', -1), ATC_TOO_LARGE), 'padding must be >= 0'),
+       ('atc_empty_valid_against_too_large', (ATC,), both(setter('num_valid', 0), ATC_TOO_LARGE), 'valid(k) is empty')]
 )
 
 
